@@ -17,6 +17,7 @@ from .hostview import (HostView, STNode, STNODE_DTYPE, UNKNOWN, make_host_view, 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCSA2_HIP_LIB") or os.path.join(_HERE, "lib", "libgcsa2_hip.so")   # override: A/B runs of two builds
 
+STATUS_BUFFER_TOO_SMALL = -6
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -30,7 +31,7 @@ EXPORTS = [
     "gcsa2_count_batch", "gcsa2_count_device",
     "gcsa2_locate_run", "gcsa2_locate_fetch", "gcsa2_locate_discard", "gcsa2_locate_device", "gcsa2_locate_into",
     "gcsa2_parent_batch", "gcsa2_parent_device", "gcsa2_depth_batch", "gcsa2_sv_batch",
-    "gcsa2_rmq_batch", "gcsa2_locate_max", "gcsa2_sample_range_batch", "gcsa2_sample_batch",
+    "gcsa2_rmq_batch", "gcsa2_locate_max", "gcsa2_locate_max_batch", "gcsa2_locate_max_into", "gcsa2_sample_range_batch", "gcsa2_sample_batch",
     "gcsa2_sampled_positions", "gcsa2_sigma", "gcsa2_fast_chars", "gcsa2_alphabet", "gcsa2_derive_comp2char",
     "gcsa2_lcp_size", "gcsa2_lcp_values", "gcsa2_lcp_levels", "gcsa2_lcp_branching",
     "gcsa2_lcp_access_batch",
@@ -117,6 +118,8 @@ def load_library():
     L.gcsa2_sv_batch.argtypes = [vp, i32, u64p, u64, u64p]
     L.gcsa2_rmq_batch.argtypes = [vp, u64p, u64, u64p]
     L.gcsa2_locate_max.argtypes = [vp, u64, u64, u64, u64p, u64, u64p]
+    L.gcsa2_locate_max_batch.argtypes = [vp, u64p, u64, u64, u64p, u64p, u64, u64p]
+    L.gcsa2_locate_max_into.argtypes = [vp, vp, u64, u64, vp, vp, u64, u64p, vp]
     L.gcsa2_sample_range_batch.argtypes = [vp, u64p, u64, u64p]
     L.gcsa2_sample_batch.argtypes = [vp, u64p, u64, u64p, u8p]
     L.gcsa2_alphabet.argtypes = [vp, u8p, u64p]
@@ -499,6 +502,26 @@ class GCSA:
         _check(self._L.gcsa2_locate_max(self._h, rng[0], rng[1], max_positions, _p64(values), cap, C.byref(cnt)))
         return values[: cnt.value]
 
+    def locate_max_batch(self, ranges, max_positions):
+        """locate(range, max_positions) for every range (gcsa2_locate_max_batch): CSR (offsets[nq+1], values), where
+        offsets[q+1] - offsets[q] = min(max_positions, count(range q)) and each range's values are those of `locate`."""
+        ranges = _ranges(ranges)
+        nq = ranges.shape[0]
+        mx = int(max_positions)
+        # room for min(max_positions, count) per range, in Python integers; a count() that wrapped below zero says nothing
+        # of the range's size, so the call is repeated with the size it asks for when this is not enough
+        cap = sum(min(mx, int(c)) for c in self.count_batch(ranges) if int(c) < (1 << 40)) if nq else 0
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        for _ in range(2):
+            values = np.zeros(max(cap, 1), dtype=np.uint64)
+            rc = self._L.gcsa2_locate_max_batch(self._h, _p64(ranges), nq, mx, _p64(offsets), _p64(values), cap, C.byref(total))
+            if rc != STATUS_BUFFER_TOO_SMALL or total.value <= cap:
+                break
+            cap = total.value
+        _check(rc)
+        return offsets, values[: total.value]
+
     def compare_kmers(self, other, k, include_Ns=False, force=False):
         """`compareKMers(self, other, k)` (reference src/algorithms.cpp:534-616): (shared, left, right)."""
         out = np.zeros(3, dtype=np.uint64)
@@ -656,6 +679,18 @@ class GCSA:
         Gcsa2Error (BUFFER_TOO_SMALL, `.needed` = values required) when capacity is insufficient."""
         total = C.c_uint64()
         rc = self._L.gcsa2_locate_into(self._h, d_ranges, nq, int(sort), d_offsets, d_values, capacity, C.byref(total), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = total.value
+            raise err
+        return total.value
+
+    def locate_max_into(self, d_ranges, nq, max_positions, d_offsets, d_values, capacity, stream=0):
+        """locate(range, max_positions) of nq device ranges into caller-owned device buffers; returns the number of values.
+        Raises Gcsa2Error (BUFFER_TOO_SMALL, `.needed` = values required) when capacity is insufficient."""
+        total = C.c_uint64()
+        rc = self._L.gcsa2_locate_max_into(self._h, d_ranges, nq, int(max_positions), d_offsets, d_values, capacity,
+                                           C.byref(total), stream)
         if rc != 0:
             err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
             err.needed = total.value

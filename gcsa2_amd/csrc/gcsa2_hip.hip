@@ -36,6 +36,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 using namespace g2;
@@ -43,6 +44,7 @@ using namespace g2;
 #include "kernels_common.hpp"
 #include "kernels_find.hpp"
 #include "kernels_locate.hpp"
+#include "kernels_locate_max.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
@@ -2796,6 +2798,264 @@ int gcsa2_locate_max(const gcsa2_index* ix, uint64_t sp, uint64_t ep, uint64_t m
   *count_out = results.size();
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_locate_max: ") + e.what()); }
+}
+
+}  // extern "C"
+
+namespace {
+// GCSA::locate(range, max_positions) of one range for the batch's host path: the reference's control flow and draws, like
+// gcsa2_locate_max, with every loop bounded.  In the random branch the range's distinct values are counted first: with fewer
+// than m of them the reference's loop never ends, and the call fails instead.  The draws then go 256 at a time through one
+// locate pass (a copy of the generator makes them; the generator itself advances by the draws used), at most 64 m + 64 of
+// them, as in the kernel.
+int locate_max_bounded(const gcsa2_index* ix, u64 sp, u64 ep, u64 max_positions, std::vector<u64>& results)
+{
+  results.clear();
+  u64 range[2] = {sp, ep}, total = 0;
+  int rc = gcsa2_count_batch(ix, range, 1, &total);
+  if(rc != GCSA2_OK) { return rc; }
+  if(total == 0) { return GCSA2_OK; }
+  const u64 m = (max_positions < total ? max_positions : total);
+  std::mt19937_64 rng(sp ^ ep);
+  auto locate_ranges = [&](const std::vector<u64>& rr, int sort, std::vector<u64>& offs, std::vector<u64>& dst) -> int
+  {
+    const u64 n = rr.size() / 2;
+    offs.assign(n + 1, 0);
+    gcsa2_locate_job* job = nullptr;
+    int r = gcsa2_locate_run(ix, rr.data(), n, sort, offs.data(), &job);
+    if(r != GCSA2_OK) { return r; }
+    dst.resize(offs[n] > 0 ? offs[n] : 1);
+    r = gcsa2_locate_fetch(job, dst.data(), dst.size());
+    dst.resize(offs[n]);
+    return r;
+  };
+  std::vector<u64> offs;
+  rc = locate_ranges({sp, ep}, 1, offs, results);               // every distinct value (gcsa.cpp:855-858)
+  if(rc != GCSA2_OK) { return rc; }
+  if(m < total / 2)                                              // random positions (gcsa.cpp:859-871)
+  {
+    if(results.size() < m)
+    {
+      return fail(GCSA2_ERR_INVALID_ARGUMENT, "locate_max: range (" + std::to_string(sp) + ", " + std::to_string(ep) + ") has " +
+                  std::to_string(results.size()) + " distinct values, fewer than max_positions and count() (" + std::to_string(total) +
+                  ") would make the reference draw forever");
+    }
+    const u64 most = 64 * m + 64;                                // m <= the range's distinct values < 2^40
+    std::unordered_set<u64> found;
+    std::vector<u64> batch, boffs, bvals;
+    u64 draws = 0;
+    while(found.size() < m)
+    {
+      if(draws >= most)
+      {
+        return fail(GCSA2_ERR_INVALID_ARGUMENT, "locate_max: range (" + std::to_string(sp) + ", " + std::to_string(ep) +
+                    ") drew 64 * max_positions + 64 positions without finding max_positions distinct values");
+      }
+      const u64 want = (most - draws < 256 ? most - draws : 256);
+      std::mt19937_64 ahead = rng;
+      batch.clear();
+      for(u64 k = 0; k < want; k++) { const u64 pos = sp + ahead() % (ep + 1 - sp); batch.push_back(pos); batch.push_back(pos); }
+      rc = locate_ranges(batch, 0, boffs, bvals);
+      if(rc != GCSA2_OK) { return rc; }
+      u64 used = want;
+      for(u64 k = 0; k < want; k++)
+      {
+        for(u64 i = boffs[k]; i < boffs[k + 1]; i++) { found.insert(bvals[i]); }
+        if(found.size() >= m) { used = k + 1; break; }
+      }
+      rng.discard(used); draws += used;
+    }
+    results.assign(found.begin(), found.end());
+  }
+  if(results.size() > m)                                         // deterministicShuffle + truncate (gcsa.cpp:873-877)
+  {
+    std::sort(results.begin(), results.end());
+    for(u64 i = results.size(); i > 0; i--) { std::swap(results[i - 1], results[rng() % i]); }
+    results.resize(m);
+  }
+  std::sort(results.begin(), results.end());
+  return GCSA2_OK;
+}
+
+// Batched locate(range, max_positions) (kernels_locate_max.hpp): sizes min(max_positions, count) -- a range with a wrapped
+// count() answered on the host first and given its real size --, their exclusive scan into d_offsets, the total read back,
+// the value buffer from `provide`, one wavefront per range, then the ranges beyond the kernel's LDS budget through
+// locate_max_bounded.  A range with fewer values than its slot (count() overstating its distinct values, which the reference
+// allows) leaves a gap that is closed on the host, offsets included.  Synchronous.  Nothing is written to the values when
+// `provide` refuses their number.
+int locate_max_core(const gcsa2_index* ix, const u64* d_ranges, u64 nq, u64 max_positions, u64* d_offsets,
+                    const std::function<int(u64, u64**)>& provide, u64* total_out, hipStream_t st)
+{
+  *total_out = 0;
+  if(nq >= LMAX_BATCH) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "locate_max batch of >= 2^24 ranges; split the batch"); }
+  if(nq == 0) { HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(u64), st)); HIP_TRY(hipStreamSynchronize(st)); return GCSA2_OK; }
+  struct Bufs
+  {
+    hipStream_t st; u64* sizes = nullptr; u64* list = nullptr; u64* odd = nullptr; void* tmp = nullptr; unsigned long long* ctl = nullptr;
+    ~Bufs() { for(void* p : {(void*)sizes, (void*)list, (void*)odd, tmp, (void*)ctl}) { if(p) { (void)hipFreeAsync(p, st); } } }
+  } b{st};
+  HIP_TRY(pool_alloc(ix, reinterpret_cast<void**>(&b.sizes), (nq + 1) * sizeof(u64), st));
+  HIP_TRY(pool_alloc(ix, reinterpret_cast<void**>(&b.list), nq * sizeof(u64), st));
+  HIP_TRY(pool_alloc(ix, reinterpret_cast<void**>(&b.odd), nq * sizeof(u64), st));
+  HIP_TRY(pool_alloc(ix, reinterpret_cast<void**>(&b.ctl), 4 * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(b.ctl, 0, 4 * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(b.ctl + 2, 0xFF, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_locate_max_sizes, dim3(grid_for(nq + 1)), dim3(TPB), 0, st, ix->img, d_ranges, nq, max_positions, b.sizes, b.ctl, b.odd);
+  LAUNCH_CHECK("k_locate_max_sizes");
+  unsigned long long ctl[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(ctl, b.ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::vector<std::pair<u64, std::vector<u64>>> odd(ctl[3]);     // (range, values): ranges whose count() wrapped
+  if(!odd.empty())
+  {
+    std::vector<u64> list(odd.size());
+    HIP_TRY(hipMemcpy(list.data(), b.odd, list.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    std::sort(list.begin(), list.end());
+    for(size_t i = 0; i < list.size(); i++)
+    {
+      u64 r[2];
+      HIP_TRY(hipMemcpy(r, d_ranges + 2 * list[i], sizeof(r), hipMemcpyDeviceToHost));
+      odd[i].first = list[i];
+      int rc = locate_max_bounded(ix, r[0], r[1], max_positions, odd[i].second);
+      if(rc != GCSA2_OK) { return rc; }
+      const u64 size = odd[i].second.size();
+      HIP_TRY(hipMemcpy(b.sizes + list[i], &size, sizeof(u64), hipMemcpyHostToDevice));
+    }
+  }
+  size_t tmp_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, b.sizes, d_offsets, size_t(nq + 1), st));
+  HIP_TRY(pool_alloc(ix, &b.tmp, tmp_bytes, st));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(b.tmp, tmp_bytes, b.sizes, d_offsets, size_t(nq + 1), st));
+  u64 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, d_offsets + nq, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *total_out = total;
+  if(total == 0) { return GCSA2_OK; }
+  u64* d_values = nullptr;
+  const int got_values = provide(total, &d_values);
+  if(got_values != GCSA2_OK) { return got_values; }
+  const u64 grid = (nq < (u64(1) << 20) ? nq : (u64(1) << 20));
+  hipLaunchKernelGGL(k_locate_max, dim3(unsigned(grid)), dim3(64), 0, st, ix->img, d_ranges, nq, max_positions, d_offsets, d_values, b.ctl, b.list, b.sizes);
+  LAUNCH_CHECK("k_locate_max");
+  HIP_TRY(hipMemcpyAsync(ctl, b.ctl, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if(ctl[0] & (LMAX_FLAG_DRAWS | LMAX_FLAG_SLOT))
+  {
+    const std::string what = (ctl[0] & LMAX_FLAG_DRAWS) ? "drew 64 * max_positions + 64 positions without finding max_positions distinct values"
+                                                        : "changed its count() between the two passes";
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "locate_max: range " + std::to_string(ctl[2]) + " " + what +
+                                            " (count() overstates the range's values: a broken index)");
+  }
+  for(const auto& o : odd)   // their slots have their real sizes
+  {
+    u64 off = 0;
+    HIP_TRY(hipMemcpy(&off, d_offsets + o.first, sizeof(u64), hipMemcpyDeviceToHost));
+    if(!o.second.empty()) { HIP_TRY(hipMemcpy(d_values + off, o.second.data(), o.second.size() * sizeof(u64), hipMemcpyHostToDevice)); }
+  }
+  bool short_ranges = (ctl[0] & LMAX_FLAG_SIZE) != 0;
+  std::vector<std::pair<u64, u64>> short_fallbacks;         // (range, values) of per-range results shorter than their slot
+  if(ctl[1] > 0)      // beyond the LDS budget: the per-range path, written into the range's slot
+  {
+    std::vector<u64> list(ctl[1]), got;
+    HIP_TRY(hipMemcpy(list.data(), b.list, list.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    std::sort(list.begin(), list.end());
+    for(u64 q : list)
+    {
+      u64 r[2], off[2];
+      HIP_TRY(hipMemcpy(r, d_ranges + 2 * q, sizeof(r), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(off, d_offsets + q, sizeof(off), hipMemcpyDeviceToHost));
+      int rc = locate_max_bounded(ix, r[0], r[1], max_positions, got);
+      if(rc != GCSA2_OK) { return rc; }
+      const u64 cnt = got.size();
+      if(cnt > off[1] - off[0]) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "locate_max: a range's result is larger than its slot"); }
+      if(cnt < off[1] - off[0]) { short_fallbacks.emplace_back(q, cnt); short_ranges = true; }
+      if(cnt > 0) { HIP_TRY(hipMemcpy(d_values + off[0], got.data(), cnt * sizeof(u64), hipMemcpyHostToDevice)); }
+    }
+  }
+  if(short_ranges)    // ranges with fewer values than their slot (count() overstating them): close the gaps, new offsets
+  {
+    std::vector<u64> offs(nq + 1), sizes(nq), vals(total);
+    HIP_TRY(hipMemcpy(offs.data(), d_offsets, offs.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sizes.data(), b.sizes, sizes.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vals.data(), d_values, vals.size() * sizeof(u64), hipMemcpyDeviceToHost));
+    for(const auto& f : short_fallbacks) { sizes[f.first] = f.second; }
+    u64 kept = 0;
+    for(u64 q = 0; q < nq; q++)
+    {
+      const u64 from = offs[q], len = sizes[q];
+      offs[q] = kept;
+      std::memmove(vals.data() + kept, vals.data() + from, len * sizeof(u64));
+      kept += len;
+    }
+    offs[nq] = kept;
+    HIP_TRY(hipMemcpy(d_offsets, offs.data(), offs.size() * sizeof(u64), hipMemcpyHostToDevice));
+    if(kept > 0) { HIP_TRY(hipMemcpy(d_values, vals.data(), kept * sizeof(u64), hipMemcpyHostToDevice)); }
+    *total_out = kept;
+  }
+  return GCSA2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gcsa2_locate_max_into(const gcsa2_index* ix, const uint64_t* d_ranges, uint64_t nq, uint64_t max_positions, uint64_t* d_offsets,
+                          uint64_t* d_values, uint64_t capacity, uint64_t* total, void* stream)
+{
+  CHECK_INDEX(ix);
+  if(total == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total = 0;
+  if(d_offsets == nullptr || (d_ranges == nullptr && nq > 0) || (d_values == nullptr && capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = locate_checks(ix, nq);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  auto provide = [d_values, capacity](u64 count, u64** out) -> int
+  {
+    if(count > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "values buffer too small"); }
+    *out = d_values;
+    return GCSA2_OK;
+  };
+  return locate_max_core(ix, d_ranges, nq, max_positions, d_offsets, provide, total, static_cast<hipStream_t>(stream));
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_locate_max_into: ") + e.what()); }
+}
+
+int gcsa2_locate_max_batch(const gcsa2_index* ix, const uint64_t* ranges, uint64_t nq, uint64_t max_positions, uint64_t* offsets,
+                           uint64_t* values, uint64_t capacity, uint64_t* total)
+{
+  CHECK_INDEX(ix);
+  if(total == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total = 0;
+  if(offsets == nullptr || (ranges == nullptr && nq > 0) || (values == nullptr && capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = locate_checks(ix, nq);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  struct Bufs { u64* ranges = nullptr; u64* offsets = nullptr; u64* values = nullptr;
+                ~Bufs() { for(u64* p : {ranges, offsets, values}) { if(p) { (void)hipFree(p); } } } } b;
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.ranges), (nq > 0 ? 2 * nq : 1) * sizeof(u64)));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.offsets), (nq + 1) * sizeof(u64)));
+  if(nq > 0) { HIP_TRY(hipMemcpy(b.ranges, ranges, 2 * nq * sizeof(u64), hipMemcpyHostToDevice)); }
+  auto provide = [&b, capacity](u64 count, u64** out) -> int
+  {
+    if(count > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "values buffer too small"); }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b.values), count * sizeof(u64)));
+    *out = b.values;
+    return GCSA2_OK;
+  };
+  rc = locate_max_core(ix, b.ranges, nq, max_positions, b.offsets, provide, total, nullptr);
+  if(rc == GCSA2_OK || rc == GCSA2_ERR_BUFFER_TOO_SMALL) { HIP_TRY(hipMemcpy(offsets, b.offsets, (nq + 1) * sizeof(u64), hipMemcpyDeviceToHost)); }
+  if(rc != GCSA2_OK) { return rc; }
+  if(*total > 0) { HIP_TRY(hipMemcpy(values, b.values, *total * sizeof(u64), hipMemcpyDeviceToHost)); }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_locate_max_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -254,6 +254,35 @@ public:
     values.resize(offsets.back());
   }
 
+  // CSR batch of locate(range, max_positions, results): offsets[q] .. offsets[q + 1] index the values of ranges[q], as the
+  // per-range call returns them; offsets[q + 1] - offsets[q] == min(max_positions, count(ranges[q])).
+  void locate_batch(const std::vector<range_type>& ranges, size_type max_positions, std::vector<size_type>& offsets,
+                    std::vector<node_type>& values) const
+  {
+    offsets.assign(ranges.size() + 1, 0);
+    std::vector<size_type> counts(ranges.size());
+    if(!ranges.empty())
+    {
+      check(gcsa2_count_batch(handle, reinterpret_cast<const size_type*>(ranges.data()), ranges.size(), counts.data()), "GCSA::locate_batch()");
+    }
+    // room for min(max_positions, count) per range; a count() that wrapped below zero says nothing of the range's size,
+    // so the call is repeated with the size it asks for when this is not enough
+    size_type capacity = 0;
+    for(size_type c : counts) { if(c < (size_type(1) << 40)) { capacity += (max_positions < c ? max_positions : c); } }
+    size_type total = 0;
+    int rc = GCSA2_OK;
+    for(int attempt = 0; attempt < 2; attempt++)
+    {
+      values.resize(capacity ? capacity : 1);
+      rc = gcsa2_locate_max_batch(handle, reinterpret_cast<const size_type*>(ranges.data()), ranges.size(), max_positions,
+                                  offsets.data(), values.data(), capacity, &total);
+      if(rc != GCSA2_ERR_BUFFER_TOO_SMALL || total <= capacity) { break; }
+      capacity = total;
+    }
+    check(rc, "GCSA::locate_batch()");
+    values.resize(total);
+  }
+
   // ---- low-level interface (gcsa.h:137-210) ----
   size_type size() const { return header.path_nodes; }                      // gcsa.h:137-148
   bool empty() const { return size() == 0; }

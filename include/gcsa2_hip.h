@@ -309,6 +309,24 @@ int gcsa2_locate_into(const gcsa2_index* index, const uint64_t* d_ranges, uint64
 int gcsa2_locate_max(const gcsa2_index* index, uint64_t sp, uint64_t ep, uint64_t max_positions,
                      uint64_t* values, uint64_t capacity, uint64_t* count);
 
+/* The same for a batch of ranges with one max_positions, one wavefront per range on the device, value for value and in
+ * the same order as gcsa2_locate_max.  CSR output: values[offsets[q], offsets[q + 1]) are the sorted values of range q,
+ * min(max_positions, count(range q)) of them -- fewer only where count() overstates a range's distinct values, as the
+ * reference allows (the slots are sized by count() and closed up afterwards then).  A count() of 2^40 or more (one that
+ * wrapped below zero) does not size a slot: such a range is answered first and its slot is its result.  The values need room
+ * for the sum of the slots; if that exceeds capacity the call fails with GCSA2_ERR_BUFFER_TOO_SMALL (*total tells how much
+ * is needed) and no value is written.  Otherwise *total = offsets[n_queries].  Where the reference would draw forever (fewer
+ * distinct values than it waits for), the call fails with GCSA2_ERR_INVALID_ARGUMENT, at the latest after
+ * 64 max_positions + 64 draws of a range.  Batches of fewer than 2^24 ranges (GCSA2_ERR_BUFFER_TOO_SMALL otherwise: split
+ * the batch).  Host arrays; complete on return. */
+int gcsa2_locate_max_batch(const gcsa2_index* index, const uint64_t* ranges, uint64_t n_queries, uint64_t max_positions,
+                           uint64_t* offsets /* n_queries + 1 */, uint64_t* values, uint64_t capacity, uint64_t* total);
+/* Into caller-owned device buffers (d_ranges, d_offsets with n_queries + 1 entries, d_values with room for `capacity`
+ * values), with the GCSA2_ERR_BUFFER_TOO_SMALL contract of gcsa2_locate_into: nothing is written behind
+ * d_values + capacity.  Enqueued on `stream`, complete on return. */
+int gcsa2_locate_max_into(const gcsa2_index* index, const uint64_t* d_ranges, uint64_t n_queries, uint64_t max_positions,
+                          uint64_t* d_offsets, uint64_t* d_values, uint64_t capacity, uint64_t* total, void* stream);
+
 /* sampled / sampleRange / firstSample (gcsa.h:191-206): out[3q] = sampled(node),
  * out[3q+1] = sampleRange(node).first (= firstSample(node)), out[3q+2] = sampleRange(node).second. */
 int gcsa2_sample_range_batch(const gcsa2_index* index, const uint64_t* nodes, uint64_t n_queries,
