@@ -95,10 +95,9 @@ struct gcsa2_index
   u64 order = 0;
   // Host pipeline of the large host-pointer batches (gcsa2_find_batch): PIPE_LANES host threads, each with two pinned + device
   // staging sets and a stream of its own, made at the first large batch and kept (one pipelined call at a time per handle).
-  struct PipeSet { char* h = nullptr; char* d = nullptr; hipEvent_t computed = nullptr, done = nullptr; bool busy = false; u64 first = 0, count = 0; };
-  // uploads + kernel on `stream`, downloads on `down`: a stream that alternates copy directions gets two thirds of the link
-  // (tests/perf/pcie_rate.hip: 34 + 34 GB/s mixed against 54 + 22 GB/s with one direction per stream)
-  struct PipeLane { hipStream_t stream = nullptr, down = nullptr; PipeSet set[2]; };
+  struct PipeSet { char* h = nullptr; char* d = nullptr; hipEvent_t done = nullptr; bool busy = false; u64 first = 0, count = 0; };
+  // uploads, kernel and downloads on the lane's one stream: a download stream of its own per lane lost, 0.86 -> 0.51 G queries/s
+  struct PipeLane { hipStream_t stream = nullptr; PipeSet set[2]; };
   mutable std::mutex pipe_lock;
   mutable std::vector<PipeLane> pipe;
   // scratch arenas of the locate pipeline that are not in use (struct Scratch)
@@ -111,7 +110,6 @@ struct gcsa2_index
     u32 cool_down = COOL_DOWN;         // GCSA2_COOL_DOWN: characters stepped singly after a step that needed parent()
     u32 ms_refill_at = MS_REFILL_AT;   // GCSA2_MS_REFILL_AT: persistent matching statistics, idle lanes of a wave that trigger a refill
     u64 ms_grid = 0;                   // GCSA2_MS_GRID: ... most workgroups launched (0: what the device holds at once)
-    u32 sort_medium_limit = 0;         // GCSA2_SORT_MEDIUM=0 sends the 17..1024-value locate segments to the segmented radix sort
     u64 locate_split = (u64(1) << 31) - 1;   // GCSA2_LOCATE_SPLIT: most values (before deduplication) one pass of the locate pipeline handles
     u64 locate_split_queries = u64(1) << 30; // GCSA2_LOCATE_SPLIT_QUERIES: most ranges one pass handles (its lists and grids are 32-bit)
     u64 pipe_chunk = u64(1) << 18;     // GCSA2_PIPE_CHUNK (log2): patterns per chunk of the host pipeline
@@ -120,23 +118,16 @@ struct gcsa2_index
     u64 kmer_piece = u64(1) << 27;        // GCSA2_KMER_PIECE (tests): children of one piece of a countKMers / compareKMers frontier
     u64 ms_piece_bytes = u64(32) << 20;   // GCSA2_MS_PIECE_MB: pattern bytes per piece of the large host batches of matching statistics / break points
     bool pipe_blocking = false;        // GCSA2_PIPE_BLOCKING=1: the lanes' events are made with hipEventBlockingSync
-    bool pipe_split = false;           // GCSA2_PIPE_SPLIT=1: downloads on a second stream per lane
-    bool pipe_wide = false;            // GCSA2_PIPE_WIRE=16: the packed-pattern pipeline brings the ranges home as u64 pairs (A/B)
     bool ms_pieces = true;             // GCSA2_MS_PIECES=0: large host batches of matching statistics go through one copy in, one launch, one copy out
-    bool dedup_narrow = true;          // GCSA2_DEDUP_NARROW=0: the duplicate filter's hash table holds 64-bit words even when the index's values fit 32 bits
-    bool dedup_huge = true;            // GCSA2_DEDUP_HUGE=0 sends every locate segment of more than 8192 values to the device-wide radix sort, duplicates and all
     bool zero_copy = true;             // GCSA2_ZERO_COPY=0: small host-pointer calls copy through the arenas like large ones
-    bool poll_small = true;            // GCSA2_POLL_SMALL=0: zero-copy calls end with hipStreamSynchronize instead of a polled ticket
     u32 seed_wide = (u32(1) << 24) - 1;   // GCSA2_SEED_WIDE: seed-table entries of this many path nodes or more are marked, not stored (tests)
     bool locate_trace = false;         // GCSA2_LOCATE_TRACE=1: host-clock stamps of a locate pass on stderr (profiles/r04_locate.md)
     u32 split_target = SPLIT_TARGET;   // GCSA2_SPLIT_TARGET (tests): values per bucket k_over_split aims at
     u32 split_skew = BIG_SEGMENT;      // GCSA2_SPLIT_SKEW (tests): buckets of more values than this count as skewed and go to the radix sort
-    bool locate_split_sort = true;     // GCSA2_LOCATE_SPLIT_SORT=0: segments beyond 8192 distinct values go to the library's device-wide radix sort (round 4; A/B)
     bool locate_fused_compact = true;  // GCSA2_LOCATE_FUSED_COMPACT=0: caller-owned buffers also take the four-kernel compaction of the job interface (A/B)
     bool locate_single = true;         // GCSA2_LOCATE_SINGLE=0: batches of one-value ranges go through the general locate pipeline too (A/B)
     bool locate_fuse = true;           // GCSA2_LOCATE_FUSE=0: wide ranges of one-value path nodes go through the table pass like the others (A/B; round 6)
     u64 fuse_above = BIG_SEGMENT;      // GCSA2_LOCATE_FUSE_ABOVE (tests): path nodes from which such a range is a candidate for the fused split
-    bool split_tiled = true;           // GCSA2_SPLIT_TILED=0: k_over_split scatters value by value, as in round 5 (A/B; round 6)
     bool mailbox = true;               // GCSA2_MAILBOX=0: one-query calls of LF / count / parent / LF(node) take the launch path like any batch (A/B; round 6)
     u64 mailbox_park_us = 200;         // GCSA2_MAILBOX_PARK_US: the resident wavefront leaves after this long without a request
     u64 mailbox_life_ms = 20;          // GCSA2_MAILBOX_LIFE_MS: ... and after this long whatever happens (the next call launches it again)
@@ -505,7 +496,7 @@ public:
   hipError_t finish()
   {
     hipError_t e = hipSuccess;
-    if(zero && ix->tune.poll_small)
+    if(zero)
     {
       volatile unsigned long long* flag = reinterpret_cast<volatile unsigned long long*>(s->z + ZERO_COPY_ARENA);
       const unsigned long long ticket = ix->next_ticket.fetch_add(1);
@@ -815,18 +806,12 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
     ix->tune.cool_down = u32(knob("GCSA2_COOL_DOWN", COOL_DOWN, 0, 1000));
     ix->tune.ms_refill_at = u32(knob("GCSA2_MS_REFILL_AT", MS_REFILL_AT, 1, 64));
     ix->tune.ms_grid = u64(knob("GCSA2_MS_GRID", 0, 0, long(1) << 30));
-    ix->tune.sort_medium_limit = (knob("GCSA2_SORT_MEDIUM", 1, 0, 1) == 0 ? SMALL_SEGMENT : MEDIUM_SEGMENT);
     ix->tune.locate_split = u64(knob("GCSA2_LOCATE_SPLIT", (long(1) << 31) - 1, 2, (long(1) << 31) - 1));
     ix->tune.locate_split_queries = u64(knob("GCSA2_LOCATE_SPLIT_QUERIES", long(1) << 30, 1, long(1) << 30));
     ix->tune.zero_copy = (knob("GCSA2_ZERO_COPY", 1, 0, 1) != 0);
-    ix->tune.poll_small = (knob("GCSA2_POLL_SMALL", 1, 0, 1) != 0);
-    ix->tune.dedup_huge = (knob("GCSA2_DEDUP_HUGE", 1, 0, 1) != 0);
-    ix->tune.dedup_narrow = (knob("GCSA2_DEDUP_NARROW", 1, 0, 1) != 0);
     ix->tune.pipe_lanes = u32(knob("GCSA2_PIPE_LANES", 6, 1, 16));
     ix->tune.pipe_chunk = u64(1) << knob("GCSA2_PIPE_CHUNK", 18, 15, 20);
-    ix->tune.pipe_split = (knob("GCSA2_PIPE_SPLIT", 0, 0, 1) != 0);
     ix->tune.pipe_blocking = (knob("GCSA2_PIPE_BLOCKING", 0, 0, 1) != 0);
-    ix->tune.pipe_wide = (knob("GCSA2_PIPE_WIRE", 0, 0, 16) == 16);
     ix->tune.ms_pieces = (knob("GCSA2_MS_PIECES", 1, 0, 1) != 0);
     ix->tune.ms_piece_bytes = u64(knob("GCSA2_MS_PIECE_MB", 32, 1, 1024)) << 20;
     ix->tune.ms_threads = u32(knob("GCSA2_MS_THREADS", 4, 1, 16));
@@ -840,8 +825,6 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
     ix->tune.mailbox = (knob("GCSA2_MAILBOX", 1, 0, 1) != 0);
     ix->tune.mailbox_park_us = u64(knob("GCSA2_MAILBOX_PARK_US", 200, 1, 1000000));
     ix->tune.mailbox_life_ms = u64(knob("GCSA2_MAILBOX_LIFE_MS", 20, 1, 10000));
-    ix->tune.split_tiled = (knob("GCSA2_SPLIT_TILED", 1, 0, 1) != 0);
-    ix->tune.locate_split_sort = (knob("GCSA2_LOCATE_SPLIT_SORT", 1, 0, 1) != 0);
     ix->tune.split_skew = u32(knob("GCSA2_SPLIT_SKEW", BIG_SEGMENT, 16, BIG_SEGMENT));
     ix->tune.split_target = u32(knob("GCSA2_SPLIT_TARGET", SPLIT_TARGET, 1, 4096));
     ix->tune.arena_cap = size_t(knob("GCSA2_ARENA_CAP_MB", 24576, 0, long(1) << 20)) << 20;    // 24 GB: 1/12 of an MI355X's HBM per arena
@@ -1202,10 +1185,8 @@ void release_host_staging(gcsa2_index* ix)
       if(set.h) { (void)hipHostFree(set.h); }
       if(set.d) { (void)hipFree(set.d); }
       if(set.done) { (void)hipEventDestroy(set.done); }
-      if(set.computed) { (void)hipEventDestroy(set.computed); }
     }
     if(lane.stream) { (void)hipStreamDestroy(lane.stream); }
-    if(lane.down) { (void)hipStreamDestroy(lane.down); }
   }
   ix->pipe.clear();
   std::lock_guard<std::mutex> staging_guard(ix->staging_lock);
@@ -1570,9 +1551,8 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
     scratch.settled = false;
   }
   // Round 6: a wide range whose path nodes have one value each does not go through the table pass -- the workgroup that splits
-  // its values reads them from the locate table itself (k_classify_fused, k_over_split): (sorted mode, table, split sort)
-  const bool fuse = (sort && ix->img.locate_tab != nullptr && ix->tune.locate_fuse && ix->tune.dedup_huge && ix->tune.locate_split_sort
-                     && ix->img.sample_width < 63);
+  // its values reads them from the locate table itself (k_classify_fused, k_over_split): (sorted mode, table)
+  const bool fuse = (sort && ix->img.locate_tab != nullptr && ix->tune.locate_fuse && ix->img.sample_width < 63);
   const u64 fuse_above = (fuse ? ix->tune.fuse_above : 0);
   HIP_TRY(scratch.get(sizes, 3 * (nq + 1))); HIP_TRY(scratch.get(segs, 7 * nq));
   u64 *node_counts = sizes, *raw_counts = sizes + (nq + 1), *node_off = sizes + 2 * (nq + 1), *raw_off = d_offsets;
@@ -1596,11 +1576,10 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, node_counts, node_off, size_t(nq + 1), stream));
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, raw_counts, raw_off, size_t(nq + 1), stream));
   // segments with more than one raw value: the only ones removeDuplicates has to touch
-  const u32 medium_limit = ix->tune.sort_medium_limit;
-  // with the duplicate filter every segment beyond the medium class goes through it first (listed as huge), without it only
-  // the ones the workgroup sort cannot hold
-  const u32 big_limit = (ix->tune.dedup_huge && sort ? (medium_limit > SMALL_SEGMENT ? medium_limit : SMALL_SEGMENT) : BIG_SEGMENT);
-  hipLaunchKernelGGL(k_collect_multi, dim3(unsigned((nq + COLLECT_THREADS - 1) / COLLECT_THREADS)), dim3(COLLECT_THREADS), 0, stream, node_off, raw_off, nq, d_totals, seg_begin, seg_end, huge_begin, huge_end, medium_limit, big_limit,
+  // sorted, every segment beyond the medium class goes through the duplicate filter first (listed as huge); unsorted, only the
+  // ones the workgroup sort cannot hold
+  const u32 big_limit = (sort ? MEDIUM_SEGMENT : BIG_SEGMENT);
+  hipLaunchKernelGGL(k_collect_multi, dim3(unsigned((nq + COLLECT_THREADS - 1) / COLLECT_THREADS)), dim3(COLLECT_THREADS), 0, stream, node_off, raw_off, nq, d_totals, seg_begin, seg_end, huge_begin, huge_end, MEDIUM_SEGMENT, big_limit,
                      d_ranges, ix->img.locate_tab, over_begin, over_end, over_src);
   LAUNCH_CHECK("k_collect_multi");
   unsigned long long totals[TOTAL_WORDS];
@@ -1690,49 +1669,39 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
   // removeDuplicates: queries with up to SMALL_SEGMENT values are sorted in registers, up to MEDIUM_SEGMENT by a wavefront
   // and up to BIG_SEGMENT by a workgroup in LDS, all in place.  Longer ones first lose their duplicates (k_dedup_huge) and
   // join those lists with their distinct values (the sorts are launched over upper bounds of the list lengths and read the
-  // lengths on the device); a segment with more than BIG_SEGMENT distinct values is listed for the device-wide radix sort
-  // over (segment, value) keys.  Then flag + scan + compact.
+  // lengths on the device); a segment with more than BIG_SEGMENT distinct values is split into buckets (k_over_split), and a
+  // skewed bucket goes to the device-wide radix sort over (segment, value) keys.  Then flag + scan + compact.
   u64 over = totals[T_OVER], over_values = totals[T_OVER_VALUES];      // (the fused ranges: k_collect_multi listed them)
   const u64 huge = huge_a + huge_b;
   // the slots behind the distinct values of a filtered segment are marked in a bitmap instead of being filled and read again
   // (k_dedup_huge, k_mark_compact) -- when the one-sweep compaction is the one that will run
   // (an index whose values lie below 2^32 -- samples of at most 31 bits + fewer than 2^23 steps -- gets the 32-bit hash table)
-  const bool narrow_values = (ix->img.sample_width <= 31 && ix->tune.dedup_narrow);
+  const bool narrow_values = (ix->img.sample_width <= 31);
   unsigned long long* dead = nullptr;
-  if(huge > 0 && ix->tune.dedup_huge && known_out != nullptr && ix->tune.locate_fused_compact)
+  if(huge > 0 && known_out != nullptr && ix->tune.locate_fused_compact)
   {
     HIP_TRY(scratch.get(dead, nwords));
     HIP_TRY(hipMemsetAsync(dead, 0, nwords * sizeof(unsigned long long), stream));
   }
-  if(huge > 0 && !ix->tune.dedup_huge)
-  {
-    // (A/B knob: no duplicate filter; every segment of more than BIG_SEGMENT values -- all on the second list -- goes to the radix sort)
-    HIP_TRY(hipMemsetAsync(over_src, 0, nq * sizeof(u64), stream));      // (no fused ranges without the filter: every segment is read from the raw values)
-    hipLaunchKernelGGL(k_huge_to_over, dim3(grid_for(huge_b)), dim3(TPB), 0, stream, huge_begin, huge_end, nq - 1, huge_b, over_begin, over_end, d_totals);
-    LAUNCH_CHECK("k_huge_to_over");
-    rc = read_totals(ix, slot, totals, stream);
-    if(rc != GCSA2_OK) { return rc; }
-    over = totals[T_OVER]; over_values = totals[T_OVER_VALUES];
-  }
-  else if(huge_a > 0)
+  if(huge_a > 0)
   {
     // (64-bit words for the short segments whatever the index: with 32-bit words -- 32 KB, five workgroups on a CU instead of two --
     // this kernel was SLOWER on the 2^23 repeat graph, 0.81 against 0.62 ms for the 32-mer batch; the long segments' kernel gains, 3.6 -> 2.9 ms)
     hipLaunchKernelGGL((k_dedup_huge<BIG_SEGMENT, false, 512, unsigned long long>), dim3(unsigned(huge_a)), dim3(512), 0, stream, huge_begin, huge_end, nq - 1, sorted, nq,
-                       medium_limit, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
+                       MEDIUM_SEGMENT, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
     LAUNCH_CHECK("k_dedup_huge");
   }
-  if(huge_b > 0 && ix->tune.dedup_huge)
+  if(huge_b > 0)
   {
     if(narrow_values)
     {
       hipLaunchKernelGGL((k_dedup_huge<2 * BIG_SEGMENT, true, 1024, u32>), dim3(unsigned(huge_b)), dim3(1024), 0, stream, huge_begin, huge_end, nq - 1, sorted, nq,
-                         medium_limit, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
+                         MEDIUM_SEGMENT, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
     }
     else
     {
       hipLaunchKernelGGL((k_dedup_huge<2 * BIG_SEGMENT, true, 1024, unsigned long long>), dim3(unsigned(huge_b)), dim3(1024), 0, stream, huge_begin, huge_end, nq - 1, sorted, nq,
-                         medium_limit, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
+                         MEDIUM_SEGMENT, d_totals, seg_begin, seg_end, over_begin, over_end, over_src, dead);
     }
     LAUNCH_CHECK("k_dedup_huge");
     stamp(2);
@@ -1797,10 +1766,10 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
     }
     return GCSA2_OK;
   };
-  if(over > 0 && ix->tune.locate_split_sort)
+  if(over > 0)
   {
     // segments of more than BIG_SEGMENT distinct values: one workgroup each splits its segment into buckets that the
-    // workgroup sort holds (k_over_split); what a skewed segment leaves over goes to the device-wide radix sort as before
+    // workgroup sort holds (k_over_split); what a skewed segment leaves over goes to the device-wide radix sort
     const u64 bucket_cap = over_values / 64 + over + 16;                  // listed buckets have more than 64 values
     u64 *split_tmp = nullptr, *bkt_begin = nullptr, *bkt_end = nullptr, *skew_begin = nullptr, *skew_end = nullptr;
     HIP_TRY(scratch.get(split_tmp, total_raw));
@@ -1811,16 +1780,8 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
     const u64 mid_cap = over_values / BUCKET_BY_WAVE + over + 16;         // buckets of 513 .. 1024 values
     u64 *mid_begin = nullptr, *mid_end = nullptr;
     HIP_TRY(scratch.get(mid_begin, mid_cap)); HIP_TRY(scratch.get(mid_end, mid_cap));
-    if(ix->tune.split_tiled)
-    {
-      hipLaunchKernelGGL(k_over_split<true>, dim3(unsigned(over)), dim3(SPLIT_THREADS), 0, stream, over_begin, over_end, sorted, split_tmp,
-                         bkt_begin, bkt_end, skew_begin, skew_end, d_totals, skew_above, ix->tune.split_target, bucket_cap - 1, over_src, mid_begin, mid_end);
-    }
-    else
-    {
-      hipLaunchKernelGGL(k_over_split<false>, dim3(unsigned(over)), dim3(SPLIT_THREADS), 0, stream, over_begin, over_end, sorted, split_tmp,
-                         bkt_begin, bkt_end, skew_begin, skew_end, d_totals, skew_above, ix->tune.split_target, bucket_cap - 1, over_src, mid_begin, mid_end);
-    }
+    hipLaunchKernelGGL(k_over_split, dim3(unsigned(over)), dim3(SPLIT_THREADS), 0, stream, over_begin, over_end, sorted, split_tmp,
+                       bkt_begin, bkt_end, skew_begin, skew_end, d_totals, skew_above, ix->tune.split_target, bucket_cap - 1, over_src, mid_begin, mid_end);
     LAUNCH_CHECK("k_over_split");
     rc = read_totals(ix, slot, totals, stream);
     if(rc != GCSA2_OK) { return rc; }
@@ -1845,7 +1806,6 @@ int locate_chunk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, int sort, u
     }
     if(skew > 0) { rc = radix_over(skew_begin, skew_end, skew, skew_values); if(rc != GCSA2_OK) { return rc; } }
   }
-  else if(over > 0) { rc = radix_over(over_begin, over_end, over, over_values); if(rc != GCSA2_OK) { return rc; } }
   if(in_place && !force_compact)
   {
     // every value is sorted in the caller's buffer, at the offsets of the size scan (d_offsets): if no sort met a duplicate, that
@@ -2142,13 +2102,11 @@ int pipe_prepare(const gcsa2_index* ix)
   for(gcsa2_index::PipeLane& lane : lanes)
   {
     if(e == hipSuccess) { e = hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking); }
-    if(e == hipSuccess) { e = hipStreamCreateWithFlags(&lane.down, hipStreamNonBlocking); }
     for(gcsa2_index::PipeSet& set : lane.set)
     {
       if(e == hipSuccess) { e = hipHostMalloc(reinterpret_cast<void**>(&set.h), pipe_set_bytes(ix->tune.pipe_chunk), hipHostMallocDefault); }
       if(e == hipSuccess) { e = hipMalloc(reinterpret_cast<void**>(&set.d), pipe_set_bytes(ix->tune.pipe_chunk)); }
       if(e == hipSuccess) { e = hipEventCreateWithFlags(&set.done, hipEventDisableTiming | (ix->tune.pipe_blocking ? hipEventBlockingSync : 0)); }
-      if(e == hipSuccess) { e = hipEventCreateWithFlags(&set.computed, hipEventDisableTiming); }
     }
   }
   if(e != hipSuccess)
@@ -2158,10 +2116,8 @@ int pipe_prepare(const gcsa2_index* ix)
       for(gcsa2_index::PipeSet& set : lane.set)
       {
         if(set.h) { (void)hipHostFree(set.h); } if(set.d) { (void)hipFree(set.d); } if(set.done) { (void)hipEventDestroy(set.done); }
-        if(set.computed) { (void)hipEventDestroy(set.computed); }
       }
       if(lane.stream) { (void)hipStreamDestroy(lane.stream); }
-      if(lane.down) { (void)hipStreamDestroy(lane.down); }
     }
     return fail(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("host pipeline: ") + hipGetErrorString(e));
   }
@@ -2170,12 +2126,12 @@ int pipe_prepare(const gcsa2_index* ix)
 }
 
 // The ranges of a chunk travel home as (sp, length) pairs in the narrowest exact form (comm.hpp: k_pack_ranges32 / 40): 8 bytes
-// per query below 2^32 path nodes and edges, 10 below 2^40, else the 16 bytes of the u64 pairs.  GCSA2_PIPE_WIRE=16 keeps the wide
-// form (A/B).  A lane widens them into the caller's array when it retires the chunk.
+// per query below 2^32 path nodes and edges, 10 below 2^40, else the 16 bytes of the u64 pairs.  A lane widens them into the
+// caller's array when it retires the chunk.
 inline u64 pipe_wire_bytes(const gcsa2_index* ix)
 {
   const u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
-  return (ix->tune.pipe_wide ? 16 : (top < (u64(1) << 32) ? 8 : (top < (u64(1) << 40) ? 10 : 16)));
+  return (top < (u64(1) << 32) ? 8 : (top < (u64(1) << 40) ? 10 : 16));
 }
 
 inline void pipe_widen(const char* h, u64 count, u64 wire, u64* dst)
@@ -2238,7 +2194,6 @@ int find_pipelined(const gcsa2_index* ix, const uint8_t* patterns, const uint64_
   const bool direct_pat = page_locked(patterns, offsets[nq] - offsets[0]), direct_off = page_locked(offsets, (nq + 1) * sizeof(u64)),
              direct_out = page_locked(ranges, 2 * nq * sizeof(u64));
   const unsigned PIPE_LANES = ix->tune.pipe_lanes;
-  const bool split = ix->tune.pipe_split;
   // pageable result arrays are filled by the lanes anyway: their ranges come home in the narrow form (the pattern bytes of the
   // chunk have been consumed by then: their place in both staging buffers takes it); a page-locked array is written in place
   const u64 wire = (direct_out ? 16 : pipe_wire_bytes(ix));
@@ -2303,28 +2258,21 @@ int find_pipelined(const gcsa2_index* ix, const uint8_t* patterns, const uint64_
       const uint8_t* d_first = reinterpret_cast<const uint8_t*>(d_pat + phase) - (direct_off && !uniform ? base : 0);
       int rc_find = gcsa2_find_device(ix, d_first, d_off, count, d_out, lane.stream);
       if(rc_find != GCSA2_OK) { status[t] = rc_find; messages[t] = g_error; break; }
-      hipStream_t back = lane.stream;
-      if(split)
+      if(wire != 16)
       {
-        back = lane.down;
-        err = hipEventRecord(set.computed, lane.stream);
-        if(err == hipSuccess) { err = hipStreamWaitEvent(lane.down, set.computed, 0); }
-      }
-      if(err == hipSuccess && wire != 16)
-      {
-        const int rc_pack = (wire == 10 ? gcsa2_pack_ranges40_device(d_out, count, set.d, back) : gcsa2_pack_ranges32_device(d_out, count, reinterpret_cast<uint32_t*>(set.d), back));
+        const int rc_pack = (wire == 10 ? gcsa2_pack_ranges40_device(d_out, count, set.d, lane.stream) : gcsa2_pack_ranges32_device(d_out, count, reinterpret_cast<uint32_t*>(set.d), lane.stream));
         if(rc_pack != GCSA2_OK) { status[t] = rc_pack; messages[t] = g_error; break; }
-        err = hipMemcpyAsync(set.h, set.d, count * wire, hipMemcpyDeviceToHost, back);
+        err = hipMemcpyAsync(set.h, set.d, count * wire, hipMemcpyDeviceToHost, lane.stream);
       }
-      else if(err == hipSuccess) { err = hipMemcpyAsync(direct_out ? reinterpret_cast<char*>(ranges + 2 * b) : h_out, d_out, count * 16, hipMemcpyDeviceToHost, back); }
-      if(err == hipSuccess) { err = hipEventRecord(set.done, back); }
+      else { err = hipMemcpyAsync(direct_out ? reinterpret_cast<char*>(ranges + 2 * b) : h_out, d_out, count * 16, hipMemcpyDeviceToHost, lane.stream); }
+      if(err == hipSuccess) { err = hipEventRecord(set.done, lane.stream); }
       if(err != hipSuccess) { fail_lane("hipMemcpyAsync / hipEventRecord", err); break; }
       set.busy = true; set.first = b; set.count = count;
     }
     for(gcsa2_index::PipeSet& set : lane.set) { if(status[t] == GCSA2_OK) { (void)retire(set); } }
     if(status[t] != GCSA2_OK)           // nothing of this call may still be in flight when it returns
     {
-      (void)hipStreamSynchronize(lane.stream); (void)hipStreamSynchronize(lane.down);
+      (void)hipStreamSynchronize(lane.stream);
       for(gcsa2_index::PipeSet& set : lane.set) { set.busy = false; }
     }
   };
@@ -2368,7 +2316,7 @@ int find_packed_pipelined(const gcsa2_index* ix, const uint64_t* codes, u64 leng
   std::vector<std::string> messages(PIPE_LANES);
   const u64 out_at = (PIPE_CHUNK_BYTES + 64) + (PIPE_CHUNK_QUERIES + 8) * 8;      // where a set keeps its ranges (pipe_set_bytes)
   // the ranges travel home as (sp, length) pairs in the narrowest exact form (comm.hpp): 8 bytes below 2^32 path nodes and
-  // edges, 10 below 2^40, else the 16 bytes of the u64 pairs; GCSA2_PIPE_WIRE=16 keeps the wide form (A/B)
+  // edges, 10 below 2^40, else the 16 bytes of the u64 pairs
   const u64 wire = pipe_wire_bytes(ix);
   auto work = [&](unsigned t)
   {

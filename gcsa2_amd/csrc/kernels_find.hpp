@@ -359,12 +359,10 @@ __device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 after2, u
 // characters are fast characters; a pair that does not prove both steps non-empty is replayed as two
 // single steps (`force_single`), so every returned range is the one the single-step search returns.
 // Waves per SIMD the plain instantiations (what gcsa2_find_device runs) are compiled for.  4 = 16 waves per CU (107 VGPRs).
-// -DGCSA2_FIND_WAVES=5 gives 96 VGPRs with only the pattern and output pointers spilled, outside the step loop, and the 18
+// Five waves per SIMD give 96 VGPRs with only the pattern and output pointers spilled, outside the step loop, and the 18
 // waves per CU that LDS allows -- measured 2-5 % SLOWER (profiles/r02_occupancy.md): at 16 waves the kernel already sits at
 // the memory system's request rate, more resident chains only lengthen each one's round trip.
-#ifndef GCSA2_FIND_WAVES
-#define GCSA2_FIND_WAVES 4
-#endif
+constexpr int FIND_WAVES = 4;
 // PACKED = true (gcsa2_find_packed_device): the patterns arrive as 2-bit codes, all of one length `offsets` (the argument is
 // then the LENGTH, not an array), last character first -- word j of pattern q, at patterns + 8 (q W + j) with W = ceil(length /
 // 32), holds the characters at distance 32 j .. 32 j + 31 from the pattern's end, comp - 1 of the character at distance t in
@@ -372,7 +370,7 @@ __device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 after2, u
 // sends 8 bytes per 32-mer over the link instead of 32 + 8; the kernel's seed index and pattern window are the words
 // themselves.  Only fast characters can be written this way (comps 1..4: a pattern with an N takes the byte interface).
 template<bool STATS, bool JUMP = false, bool PAIR = false, bool PACKED = false>
-__global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : GCSA2_FIND_WAVES) void k_find2(DevImage img, const u8* __restrict__ patterns,
+__global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : FIND_WAVES) void k_find2(DevImage img, const u8* __restrict__ patterns,
                                                const u64* __restrict__ offsets, u64 nq,
                                                u64* __restrict__ out, unsigned long long* __restrict__ stats,
                                                const u32* __restrict__ perm)

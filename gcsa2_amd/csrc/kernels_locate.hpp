@@ -461,8 +461,9 @@ __device__ __forceinline__ u64 wg_reserve(WgSlotsOf<THREADS>& sh, unsigned long 
 // queries with 2..SMALL_SEGMENT values are sorted in registers by one lane each (k_sort_small), queries with up to
 // MEDIUM_SEGMENT values by one wavefront each in LDS (k_sort_medium), queries with up to BIG_SEGMENT values by one workgroup
 // each in 64 KB of LDS (k_sort_big: the paper's 16-mers average 7129 values, paper.tex:403); longer ones lose their duplicates
-// first (k_dedup_huge) and join those lists, and what still has more than BIG_SEGMENT DISTINCT values is sorted by ONE
-// device-wide radix sort over (segment, value) keys (k_over_pack / k_over_unpack).  k_collect_multi lists the medium
+// first (k_dedup_huge) and join those lists, and what still has more than BIG_SEGMENT DISTINCT values is split into buckets
+// by one workgroup each (k_over_split); a skewed bucket is sorted by ONE device-wide radix sort over (segment, value) keys
+// (k_over_pack / k_over_unpack).  k_collect_multi lists the medium
 // segments (from the end of the segment arrays, downwards), the large ones (from the start; MEDIUM_SEGMENT + 1 ..
 // BIG_SEGMENT values) and the huge ones (arrays of their own: up to HUGE_SPLIT values from the start, longer ones from the
 // end downwards -- the two instantiations of k_dedup_huge) and publishes the totals below.
@@ -1717,7 +1718,7 @@ __global__ __launch_bounds__(TPB) void k_locate_walk(DevImage img, const u64* __
 }
 
 // Segments with more than BIG_SEGMENT distinct values, round 5: ONE WORKGROUP PER SEGMENT sorts it.  It splits the segment on
-// the top bits of (value - the segment's smallest value) into up to 4096 buckets of a few dozen values -- minimum and
+// the top bits of (value - the segment's smallest value) into up to 512 buckets of a few hundred values -- minimum and
 // maximum, a histogram in LDS, its prefix sums, the scatter into `scratch` at the same offsets -- and then its sixteen
 // wavefronts sort the buckets, one bucket of up to 64 values per wavefront at a time, in REGISTERS (a bitonic network over the
 // lanes: 21 exchange steps, no LDS, no barrier; 32-bit keys relative to the run's base where they fit, wave_sort32) straight into
@@ -1728,12 +1729,8 @@ __global__ __launch_bounds__(TPB) void k_locate_walk(DevImage img, const u64* __
 // bitonic sort took 22 ms for them: 66 barriers per bucket, profiles/r05_locate.md).  A bucket of more than 64 values is
 // listed for the workgroup sort (k_sort_big reads `scratch`, writes `values`), one of more than `skew_above` values -- values
 // crowded into a small part of the segment's span -- goes on the `skew` list, which the host hands to that radix sort as before.
-#ifndef GCSA2_SPLIT_THREADS
-#define GCSA2_SPLIT_THREADS 1024
-#endif
-constexpr int SPLIT_THREADS = GCSA2_SPLIT_THREADS;
-constexpr u32 SPLIT_BUCKETS_UNTILED = 4096;
-// Round 6, TILED: the scatter goes through LDS a tile of SPLIT_TILE values at a time.  Untiled, the 64 lanes of a store
+constexpr int SPLIT_THREADS = 1024;
+// Round 6: the scatter goes through LDS a tile of SPLIT_TILE values at a time.  Value by value (round 5), the 64 lanes of a store
 // instruction hit ~50 different buckets: 64 eight-byte write requests where a copy sends a few lines.  The L2 merges them, but
 // it takes REQUESTS at a fixed rate: with the stores switched off the kernel took 1.7 of its 4.4 ms on the 16-mer batch of the
 // 2^30-base text (profiles/r06_locate.md; the knock-out knob is profiles/r06_locate/split_debug.patch).  Tiled, the workgroup counts the tile's values per bucket (the
@@ -1747,10 +1744,7 @@ constexpr u32 SPLIT_BUCKETS_UNTILED = 4096;
 // 32-mer batch, profiles/r06_locate.md: 256 buckets 6.84 / 6.34 ms, 512 buckets 6.82 / 6.04, 1024 buckets 7.72 / 6.79 -- every
 // wavefront reads and writes 8 KB of counts per tile --; counts held in registers across the scan cost the second workgroup
 // per CU; workgroups of 512 threads 6.99 / 5.25; tiles only for segments of up to 256 buckets 7.43 / 6.58.)
-#ifndef GCSA2_TILED_BUCKETS
-#define GCSA2_TILED_BUCKETS 512
-#endif
-constexpr u32 SPLIT_TILED_BUCKETS = GCSA2_TILED_BUCKETS;
+constexpr u32 SPLIT_TILED_BUCKETS = 512;
 constexpr u32 SPLIT_TILE_PER = 4, SPLIT_TILE = u32(SPLIT_THREADS) * SPLIT_TILE_PER;
 constexpr u32 SPLIT_SAMPLE = 8192;             // values whose minimum and maximum stand for the segment's
 constexpr u32 SPLIT_AHEAD = 4;                 // independent loads per lane in the streaming passes
@@ -1769,7 +1763,6 @@ constexpr u32 BUCKET_BY_WAVE = 512;
 
 // (waves_per_eu: two workgroups per CU, said to the register allocator -- 4.55 -> 4.43 ms and 3.30 -> 3.03 ms on the two batches
 // of the 2^30-base text)
-template<bool TILED>
 __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_over_split(const u64* __restrict__ over_begin, const u64* __restrict__ over_end,
                                                              u64* values, u64* scratch, u64* __restrict__ bkt_begin, u64* __restrict__ bkt_end,
                                                              u64* __restrict__ skew_begin, u64* __restrict__ skew_end,
@@ -1777,17 +1770,17 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
                                                              const u64* const* __restrict__ over_src,
                                                              u64* __restrict__ mid_begin, u64* __restrict__ mid_end)
 {
-  // (the tiled form never has more than SPLIT_TILED_BUCKETS buckets: its cursor / start arrays are as long as the workgroup)
-  constexpr u32 SPLIT_BUCKETS = (TILED ? u32(SPLIT_THREADS) : SPLIT_BUCKETS_UNTILED);
+  // (never more than SPLIT_TILED_BUCKETS buckets: the cursor / start arrays are as long as the workgroup)
+  constexpr u32 SPLIT_BUCKETS = u32(SPLIT_THREADS);
   __shared__ __attribute__((aligned(16))) u32 cursor[SPLIT_BUCKETS];        // histogram, then the buckets' write cursors (= their ends after the scatter)
   __shared__ u32 starts[SPLIT_BUCKETS];
   __shared__ u32 wave_sums[SPLIT_THREADS / 64];
   __shared__ unsigned long long s_lo, s_hi, list_base, big_base, skew_base, mid_base;
   __shared__ u32 wg_listed, wg_big, wg_skewed, wg_skew_values, next_chunk, wg_mid;
-  __shared__ __attribute__((aligned(16))) u32 tile_count[2][TILED ? SPLIT_TILED_BUCKETS : 4];      // values of the tile per bucket (two tiles alternate)
-  __shared__ __attribute__((aligned(16))) u32 tile_off[TILED ? SPLIT_TILED_BUCKETS : 4];           // their exclusive prefix sums
-  __shared__ __attribute__((aligned(16))) u32 tile_delta[TILED ? SPLIT_TILED_BUCKETS : 4];         // where in the segment the bucket's values of this tile go, minus tile_off
-  __shared__ u64 tile_value[TILED ? SPLIT_TILE : 1];                  // the tile, bucket by bucket
+  __shared__ __attribute__((aligned(16))) u32 tile_count[2][SPLIT_TILED_BUCKETS];      // values of the tile per bucket (two tiles alternate)
+  __shared__ __attribute__((aligned(16))) u32 tile_off[SPLIT_TILED_BUCKETS];           // their exclusive prefix sums
+  __shared__ __attribute__((aligned(16))) u32 tile_delta[SPLIT_TILED_BUCKETS];         // where in the segment the bucket's values of this tile go, minus tile_off
+  __shared__ u64 tile_value[SPLIT_TILE];                  // the tile, bucket by bucket
   constexpr u32 PER_THREAD = SPLIT_BUCKETS / SPLIT_THREADS;
   const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const u64 b = over_begin[blockIdx.x], len = over_end[blockIdx.x] - b;
@@ -1824,8 +1817,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
   lo = s_lo; hi = s_hi;
   // buckets: the smallest power of two with len / buckets <= SPLIT_TARGET, at most SPLIT_BUCKETS; bucket = (v - lo) >> shift
   u32 nb = 2;
-  const u32 most_buckets = (TILED ? SPLIT_TILED_BUCKETS : SPLIT_BUCKETS);
-  while(nb < most_buckets && u64(nb) * target < len) { nb <<= 1; }          // (target: SPLIT_TARGET; GCSA2_SPLIT_TARGET in tests)
+  while(nb < SPLIT_TILED_BUCKETS && u64(nb) * target < len) { nb <<= 1; }          // (target: SPLIT_TARGET; GCSA2_SPLIT_TARGET in tests)
   const u64 span = hi - lo;                                   // largest (v - lo)
   u32 shift = 0;
   while(shift < 63 && (span >> shift) >= nb) { shift++; }
@@ -1916,7 +1908,6 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
       at += mine[k];
     }
   }
-  if constexpr(TILED)
   {
     static_assert(SPLIT_TILED_BUCKETS % 256 == 0 && SPLIT_TILED_BUCKETS <= SPLIT_THREADS, "counts per lane in groups of four; a thread owns a bucket");
     if(tid < SPLIT_TILED_BUCKETS) { tile_count[0][tid] = 0; tile_count[1][tid] = 0; }
@@ -2012,21 +2003,6 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
       // batch of the 2^30-base text, same box, three runs each.  Wavefronts that run ahead into the next tile's atomics take the
       // LDS from the ones still reading this tile.)
       if(tid < SPLIT_TILED_BUCKETS) { cursor[tid] += count[tid]; count[tid] = 0; }
-    }
-  }
-  else
-  for(u64 i0 = tid; i0 < len; i0 += SPLIT_AHEAD * SPLIT_THREADS)
-  {
-    u64 got[SPLIT_AHEAD];
-#pragma unroll
-    for(u32 j = 0; j < SPLIT_AHEAD; j++) { const u64 i = i0 + u64(j) * SPLIT_THREADS; got[j] = (i < len ? (src[i] & KEEP) : lo); }
-#pragma unroll
-    for(u32 j = 0; j < SPLIT_AHEAD; j++)
-    {
-      if(i0 + u64(j) * SPLIT_THREADS < len)
-      {
-        scratch[b + atomicAdd(&cursor[bucket_of(got[j])], 1u)] = got[j];
-      }
     }
   }
   __syncthreads();                                             // (the workgroup's stores have completed: s_waitcnt vmcnt(0) + barrier)
@@ -2132,9 +2108,8 @@ __global__ __launch_bounds__(64) void k_sort_bucket(const u64* __restrict__ bkt_
   report_dups(totals, sort_segment_by_wave<MOST>(source + b, values + b, len, lane, ~u64(0), stage), lane);
 }
 
-// Segments with more than BIG_SEGMENT distinct values whose split left a bucket too large (k_over_split's skew list), and every
-// such segment with GCSA2_LOCATE_SPLIT_SORT=0 (A/B) (a 16-mer of an interspersed repeat matches 200 000 path nodes on the
-// repeat-rich 2^30-base text): ONE device-wide radix sort over keys (rank of the segment among those segments) << value_bits
+// Segments with more than BIG_SEGMENT distinct values whose split left a bucket too large (k_over_split's skew list) (a 16-mer
+// of an interspersed repeat matches 200 000 path nodes on the repeat-rich 2^30-base text): ONE device-wide radix sort over keys (rank of the segment among those segments) << value_bits
 // | value sorts them all at once, whatever their sizes -- round 3 gave them to the library's SEGMENTED sort, whose work per
 // segment made a batch of 16 000 such segments 100 ms.  over_off = exclusive scan of the segment lengths (over + 1 entries).
 __global__ __launch_bounds__(TPB) void k_over_lengths(const u64* __restrict__ over_begin, const u64* __restrict__ over_end, u64 over,
@@ -2171,18 +2146,6 @@ __global__ __launch_bounds__(TPB) void k_over_unpack(const u64* __restrict__ ove
   if(i >= total) { return; }
   const u64 key = keys[i], s = key >> value_bits;
   values[over_begin[s] + (i - over_off[s])] = key & ((u64(1) << value_bits) - 1);
-}
-
-// (GCSA2_DEDUP_HUGE=0, an A/B knob: the second huge list becomes the list of the radix sort as it is)
-__global__ __launch_bounds__(TPB) void k_huge_to_over(const u64* __restrict__ huge_begin, const u64* __restrict__ huge_end, u64 last, u64 count,
-                                                      u64* __restrict__ over_begin, u64* __restrict__ over_end, unsigned long long* __restrict__ totals)
-{
-  const u64 i = u64(blockIdx.x) * TPB + threadIdx.x;
-  if(i >= count) { return; }
-  const u64 b = huge_begin[last - i], e = huge_end[last - i];
-  over_begin[i] = b; over_end[i] = e;
-  atomicAdd(totals + T_OVER_VALUES, (unsigned long long)(e - b));
-  if(i == 0) { totals[T_OVER] = count; }
 }
 
 // The totals of a pass, copied to page-locked host memory the host polls (h[TOTAL_WORDS - 1] = ticket, written last): a

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host-memory find() batches by pipeline configuration (lanes, one or two streams per lane), from pageable and from
+"""Host-memory find() batches by pipeline lane count, from pageable and from
 page-locked memory, on the chr22-like index: `python tests/perf/host_pipeline.py` prints one JSON line per configuration.
 The knobs are read when the index is created, so every configuration opens its own handle."""
 import json
@@ -27,12 +27,11 @@ def main():
     p_out = torch.empty((nq, 2), dtype=torch.int64).pin_memory()
     out = np.zeros((nq, 2), dtype=np.uint64)
     want = None
-    configs = [(int(a), int(b)) for a, b in (c.split(":") for c in (sys.argv[1] if len(sys.argv) > 1 else "12:0,12:1,6:0,6:1,4:1,3:1,8:0,16:0").split(","))]
-    for lanes, split in configs:
+    configs = [int(c) for c in (sys.argv[1] if len(sys.argv) > 1 else "12,6,4,3,8,16").split(",")]
+    for lanes in configs:
         os.environ["GCSA2_PIPE_LANES"] = str(lanes)
-        os.environ["GCSA2_PIPE_SPLIT"] = str(split)
         gpu, _ = open_index(ix)
-        row = {"lanes": lanes, "split": split}
+        row = {"lanes": lanes}
         for name, a, b, c in (("pageable", flat, off, out), ("page_locked", p_flat.numpy(), p_off.numpy().view(np.uint64), p_out.numpy().view(np.uint64))):
             gpu.find_batch(a, b, out=c)
             best = None

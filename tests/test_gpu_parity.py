@@ -1530,21 +1530,24 @@ def test_locate_splits_large_batches(case, engine, monkeypatch):
         tiny.close()
 
 
-@pytest.mark.parametrize("dedup_huge", [1, 0, "wide"])
-def test_locate_segment_sizes(engine, monkeypatch, dedup_huge):
+@pytest.mark.parametrize("values", [1, "wide"])
+def test_locate_segment_sizes(engine, values):
     """removeDuplicates at every segment size class: 1 value, 2..16 (registers, one lane), 17..1024 (one wavefront in
     LDS; round 6: in registers, incl. the three- and six-register networks for up to 192 and 384 values), 1025..8192 (one workgroup in LDS), more (duplicates removed through an LDS hash set, then the LDS sorts; the
-    device-wide radix sort over (segment, value) keys when more than 8192 values are distinct -- the whole-index range here --
-    or, with GCSA2_DEDUP_HUGE=0, always), mixed in one batch and in both sort modes; ranges of consecutive path nodes of a repetitive SNP graph (many
-    duplicates per segment).  A second batch has no segment beyond 8192 values: the library sort is then not called at all."""
+    device-wide radix sort over (segment, value) keys when more than 8192 values are distinct -- the whole-index range here),
+    mixed in one batch and in both sort modes; ranges of consecutive path nodes of a repetitive SNP graph (many
+    duplicates per segment).  A second batch has no segment beyond 8192 values: the library sort is then not called at all.
+    "wide": the node values are shifted across 2^32, so the filter's hash table holds 64-bit words (an index whose values fit
+    32 bits gets 32-bit words)."""
     from oracle.oracle import OracleIndex
     from workload import builder
     g = graphs.snp_graph(30000, 0x4D1, 0x4D2, snp_period=5, node_len=16)
+    if values == "wide":
+        g.value += np.uint64((1 << 32) - int(g.value.max()) // 2)
     ix = builder.build(g, 16, sample_period=16)
-    # ("wide": the filter's hash table with 64-bit words; an index whose values fit 32 bits gets 32-bit words otherwise)
-    monkeypatch.setenv("GCSA2_DEDUP_HUGE", "1" if dedup_huge == "wide" else str(dedup_huge))
-    monkeypatch.setenv("GCSA2_DEDUP_NARROW", "0" if dedup_huge == "wide" else "1")
     gpu, lcp = engine.open_index(ix)
+    if values == "wide":
+        assert gpu.sampleBits() > 31          # k_dedup_huge<2 * BIG_SEGMENT, true, 1024, unsigned long long>
     cpu = OracleIndex(ix)
     rng = SplitMix64(0x4D3)
     ranges = []
@@ -1576,11 +1579,11 @@ def test_locate_segment_sizes(engine, monkeypatch, dedup_huge):
 
 
 @pytest.mark.parametrize("knobs", [{}, {"GCSA2_SPLIT_TARGET": "24"}, {"GCSA2_SPLIT_TARGET": "1500", "GCSA2_SPLIT_SKEW": "700"}, {"GCSA2_SPLIT_SKEW": "16"},
-                                   {"GCSA2_LOCATE_SPLIT_SORT": "0"}, {"GCSA2_LOCATE_FUSED_COMPACT": "0"}, {"values": "across 2^32"}, {"values": "across 2^32", "GCSA2_SPLIT_TARGET": "24"},
+                                   {"GCSA2_LOCATE_FUSED_COMPACT": "0"}, {"values": "across 2^32"}, {"values": "across 2^32", "GCSA2_SPLIT_TARGET": "24"},
                                    {"values": "across 2^32", "GCSA2_SPLIT_TARGET": "1500", "GCSA2_SPLIT_SKEW": "3000"},
                                    {"GCSA2_LOCATE_FUSE": "0"}, {"GCSA2_LOCATE_IN_PLACE": "0"}, {"GCSA2_LOCATE_FUSE_ABOVE": "600"},
                                    {"GCSA2_LOCATE_FUSE_ABOVE": "2", "GCSA2_SPLIT_TARGET": "24"}, {"values": "across 2^32", "GCSA2_LOCATE_FUSE_ABOVE": "600", "GCSA2_SPLIT_SKEW": "16"}],
-                         ids=["split-with-listed-buckets", "split-with-runs", "split-with-listed-and-skewed-buckets", "split-with-skewed-buckets", "radix-sort",
+                         ids=["split-with-listed-buckets", "split-with-runs", "split-with-listed-and-skewed-buckets", "split-with-skewed-buckets",
                               "four-kernel-compaction",
                               "64-bit-keys", "64-bit-keys-runs", "64-bit-keys-large-buckets",
                               "table-pass-for-every-range", "sorts-in-scratch", "fused-from-600-nodes",
@@ -1590,8 +1593,8 @@ def test_locate_many_large_distinct_segments(engine, knobs, monkeypatch):
     16-mers of interspersed repeats have on the 2^30-base text of bench.py: dozens of segments beyond the 8192 distinct values
     the LDS hash set and sorts hold.  Round 5: one workgroup per such segment splits it into buckets of a few dozen values and
     sorts them in registers, a wavefront per bucket (k_over_split); a bucket of more than 64 values is listed for the
-    workgroup sort, one that is still too large for that goes to the device-wide radix sort over (segment, value) keys, which
-    sorted all of them in round 4 (GCSA2_LOCATE_SPLIT_SORT=0) -- the test knobs make buckets of ~24 (sorted in runs inside the
+    workgroup sort, one that is still too large for that goes to the device-wide radix sort over (segment, value) keys (round 4
+    sorted every such segment that way) -- the test knobs make buckets of ~24 (sorted in runs inside the
     split) / ~256 (the default: listed for the register sorts) / ~1500 values and call more than 700 / 16 values too large, so
     that every branch runs, with node_type values below 2^32 and on both sides of it (32- and 64-bit sort keys); through the job interface
     (the value buffer is made once the total is known) and into caller-owned buffers (no wait for the total; a buffer that is

@@ -10,7 +10,7 @@ for kv in "$@"; do export "$kv"; done
 ROOT=$(pwd)
 mkdir -p $ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-ONLY="--kernel-include-regex k_locate_|k_over_|k_sort_|k_compact|k_mark_|k_dedup_huge|k_collect_multi|k_block_owners|k_word_counts|k_final_offsets|k_huge_to_over|k_classify|k_publish|DeviceScan|lookback_scan"
+ONLY="--kernel-include-regex k_locate_|k_over_|k_sort_|k_compact|k_mark_|k_dedup_huge|k_collect_multi|k_block_owners|k_word_counts|k_final_offsets|k_classify|k_publish|DeviceScan|lookback_scan"
 for m in 16 32; do
   if [ $m = 16 ]; then R=100000; else R=400000; fi
   timeout ${PASS_TIMEOUT:-900} rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/${TAG}_$m -o x -- \
