@@ -13,6 +13,7 @@
 //                       k_locate_*            GCSA::locate(range), locateInternal, removeDuplicates
 //                                                                        src/gcsa.cpp:827-842, 880-896, utils.h:350-357
 //                       k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
+//   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
 #include "sdsl_reader.hpp"
@@ -45,6 +46,7 @@ using namespace g2;
 #include "kernels_find.hpp"
 #include "kernels_locate.hpp"
 #include "kernels_locate_max.hpp"
+#include "kernels_mem.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
@@ -4699,3 +4701,319 @@ extern "C" int gcsa2_index_create_from_gcsa(const char* gcsa_path, const char* l
   gcsa2_host_view_free(st);
   return rc;
 }
+
+// ==== MEM hits: a MEM finder's count() + locate() per match in one call (kernels_mem.hpp) ==================================
+namespace {
+
+constexpr u64 MEM_SAMPLED_PART = LMAX_BATCH - 1;     // locate_max_core takes fewer than LMAX_BATCH ranges per call
+
+int mem_hits_checks(const gcsa2_index* ix, u64 min_length, int over)
+{
+  if(min_length == 0)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "mem_hits: min_length must be at least 1 (a record of length 0 carries the whole index as its range)");
+  }
+  if(over != GCSA2_MEM_OVER_SKIP && over != GCSA2_MEM_OVER_SAMPLE)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "mem_hits: unknown over-cap policy (GCSA2_MEM_OVER_SKIP or GCSA2_MEM_OVER_SAMPLE)");
+  }
+  if(!ix->img.has_lcp) { return fail(GCSA2_ERR_MISSING_COMPONENT, "index was created without an LCP array"); }
+  return locate_checks(ix, 0);
+}
+
+// The sampled class through locate_max_core: one CSR (d_offsets, ns + 1 entries; *d_values from `scratch`).  A class of
+// LMAX_BATCH ranges or more goes in parts below that limit, whose offsets are shifted and whose values are concatenated.
+int mem_sampled(const gcsa2_index* ix, const u64* d_ranges, u64 ns, u64 hit_max, u64* d_offsets, Scratch& scratch,
+                u64** d_values, u64* total_out, hipStream_t st)
+{
+  *total_out = 0;
+  *d_values = nullptr;
+  if(ns <= MEM_SAMPLED_PART)
+  {
+    auto provide = [&scratch, d_values](u64 count, u64** out) -> int { HIP_TRY(scratch.get(*d_values, count)); *out = *d_values; return GCSA2_OK; };
+    return locate_max_core(ix, d_ranges, ns, hit_max, d_offsets, provide, total_out, st);
+  }
+  struct Part { u64 q0 = 0, count = 0, total = 0; u64* d_off = nullptr; u64* d_val = nullptr; };
+  std::vector<Part> parts;
+  u64 total = 0;
+  for(u64 q0 = 0; q0 < ns; q0 += MEM_SAMPLED_PART)
+  {
+    Part part;
+    part.q0 = q0; part.count = std::min(MEM_SAMPLED_PART, ns - q0);
+    HIP_TRY(scratch.get(part.d_off, part.count + 1));
+    Part* self = &part;
+    auto provide = [&scratch, self](u64 count, u64** out) -> int { HIP_TRY(scratch.get(self->d_val, count)); *out = self->d_val; return GCSA2_OK; };
+    const int rc = locate_max_core(ix, d_ranges + 2 * q0, part.count, hit_max, part.d_off, provide, &part.total, st);
+    if(rc != GCSA2_OK) { return rc; }
+    total += part.total;
+    parts.push_back(part);
+  }
+  HIP_TRY(scratch.get(*d_values, total));
+  u64 base = 0;
+  for(const Part& part : parts)
+  {
+    if(part.total > 0) { HIP_TRY(hipMemcpyAsync(*d_values + base, part.d_val, part.total * sizeof(u64), hipMemcpyDeviceToDevice, st)); }
+    hipLaunchKernelGGL(k_shift_offsets, dim3(grid_for(part.count)), dim3(TPB), 0, st, part.d_off, part.count, base, d_offsets + part.q0);
+    LAUNCH_CHECK("k_shift_offsets");
+    base += part.total;
+  }
+  HIP_TRY(hipMemcpyAsync(d_offsets + ns, &total, sizeof(u64), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *total_out = total;
+  return GCSA2_OK;
+}
+
+// gcsa2_mem_hits_device after its argument checks (nq > 0).  Host round trips: the pattern bytes (only when the caller does
+// not know them), the break total (inside gcsa2_match_breaks_device), the class totals, those of the locate passes, the end.
+int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 nq, u64 total_bytes, u64 min_length,
+                  u64 hit_max, int over, u64* d_mem_offsets, gcsa2_mem* d_mems, u64 mem_capacity, u64* total_mems,
+                  u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  if(total_bytes == GCSA2_UNKNOWN)
+  {
+    HIP_TRY(hipMemcpyAsync(&total_bytes, d_offsets + nq, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  // 1. the break records, into scratch: room for the caller's MEM capacity or one record per 8 pattern bytes (a MEM finder's
+  //    minimum length keeps far fewer), never more than one per position and pattern; a batch that needs more runs again
+  u64 room = std::max(total_bytes / 8 + nq + 1, mem_capacity);
+  room = std::min(room, total_bytes + nq);
+  u64* brk = nullptr;
+  u64 m = 0;
+  HIP_TRY(scratch.get(brk, 4 * room));
+  int rc = gcsa2_match_breaks_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
+                                     room, &m, nullptr, nullptr, st);
+  if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && m > room)
+  {
+    room = m;
+    HIP_TRY(scratch.get(brk, 4 * room));
+    g_error.clear();
+    rc = gcsa2_match_breaks_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
+                                   room, &m, nullptr, nullptr, st);
+  }
+  if(rc != GCSA2_OK) { return rc; }
+  *total_mems = m;
+  if(m >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "mem_hits: 2^32 or more MEMs in one batch; split the batch"); }
+  if(m == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    return GCSA2_OK;
+  }
+  // 2. count() and the class of every MEM, one scan for the positions in both range lists and the full class's count() sum
+  u64 *mems = nullptr, *full = nullptr, *sampled = nullptr, *full_off = nullptr, *full_val = nullptr, *samp_off = nullptr, *samp_val = nullptr;
+  MemScan *words = nullptr, *pos = nullptr;
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(mems, 5 * m));
+  HIP_TRY(scratch.get(words, m + 1));
+  HIP_TRY(scratch.get(pos, m + 1));
+  hipLaunchKernelGGL(k_mem_classify, dim3(grid_for(m + 1)), dim3(TPB), 0, st, ix->img, brk, m, hit_max, int(over == GCSA2_MEM_OVER_SAMPLE), mems, words);
+  LAUNCH_CHECK("k_mem_classify");
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, scan_bytes, words, pos, MemScanOp(), MemScan{0, 0}, size_t(m + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveScan(scan_tmp, scan_bytes, words, pos, MemScanOp(), MemScan{0, 0}, size_t(m + 1), st));
+  MemScan sums{0, 0};
+  HIP_TRY(hipMemcpyAsync(&sums, pos + m, sizeof(MemScan), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const u64 nf = sums.cls & MEM_CLASS_LOW, ns = sums.cls >> 32;
+  HIP_TRY(scratch.get(full, 2 * nf));
+  HIP_TRY(scratch.get(sampled, 2 * ns));
+  hipLaunchKernelGGL(k_mem_compact, dim3(grid_for(m)), dim3(TPB), 0, st, mems, m, pos, full, sampled);
+  LAUNCH_CHECK("k_mem_compact");
+  // 3. the full class: straight into the caller's hits when nothing else goes there and they are known to fit (count() bounds
+  //    the distinct values of a range), otherwise into scratch
+  const bool direct = (ns == 0 && m <= mem_capacity && sums.sum < MEM_SUM_CAP && sums.sum <= hit_capacity);
+  u64 full_total = 0;
+  HIP_TRY(scratch.get(full_off, nf + 1));
+  if(direct)
+  {
+    ValuesProvider provide = [d_hits, hit_capacity](u64 count) -> u64* { return count <= hit_capacity ? d_hits : nullptr; };
+    rc = locate_core(ix, full, nf, 1, full_off, provide, &full_total, st, d_hits, hit_capacity);
+    full_val = d_hits;
+  }
+  else
+  {
+    ValuesProvider provide = [&scratch, &full_val](u64 count) -> u64*
+    {
+      const hipError_t e = scratch.get(full_val, count);
+      if(e != hipSuccess) { fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("mem_hits: values of the full class: ") + hipGetErrorString(e)); return nullptr; }
+      return full_val;
+    };
+    rc = locate_core(ix, full, nf, 1, full_off, provide, &full_total, st);
+  }
+  if(rc != GCSA2_OK) { return rc; }
+  // 4. the sampled class
+  u64 samp_total = 0;
+  if(ns > 0)
+  {
+    HIP_TRY(scratch.get(samp_off, ns + 1));
+    rc = mem_sampled(ix, sampled, ns, hit_max, samp_off, scratch, &samp_val, &samp_total, st);
+    if(rc != GCSA2_OK) { return rc; }
+  }
+  const u64 h = full_total + samp_total;
+  *total_hits = h;
+  if(m > mem_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "MEM buffer too small"); }
+  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
+  // 5. the results in MEM order
+  HIP_TRY(hipMemcpyAsync(d_mems, mems, m * sizeof(gcsa2_mem), hipMemcpyDeviceToDevice, st));
+  if(ns == 0)
+  {
+    hipLaunchKernelGGL(k_mem_spread, dim3(grid_for(m + 1)), dim3(TPB), 0, st, pos, m, full_off, d_hit_offsets);
+    LAUNCH_CHECK("k_mem_spread");
+    if(!direct && full_total > 0) { HIP_TRY(hipMemcpyAsync(d_hits, full_val, full_total * sizeof(u64), hipMemcpyDeviceToDevice, st)); }
+  }
+  else
+  {
+    u64* sizes = nullptr;
+    HIP_TRY(scratch.get(sizes, m + 1));
+    hipLaunchKernelGGL(k_mem_sizes, dim3(grid_for(m + 1)), dim3(TPB), 0, st, pos, m, full_off, samp_off, sizes);
+    LAUNCH_CHECK("k_mem_sizes");
+    size_t sum_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, sizes, d_hit_offsets, size_t(m + 1), st));
+    char* sum_tmp = nullptr;
+    HIP_TRY(scratch.get(sum_tmp, sum_bytes));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sum_tmp, sum_bytes, sizes, d_hit_offsets, size_t(m + 1), st));
+    if(h > 0)
+    {
+      hipLaunchKernelGGL(k_mem_gather, dim3(grid_for(h)), dim3(TPB), 0, st, pos, m, d_hit_offsets, h, full_off, full_val, samp_off, samp_val, d_hits);
+      LAUNCH_CHECK("k_mem_gather");
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_mem_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_pattern_bytes,
+                          uint64_t min_length, uint64_t hit_max, int over, uint64_t* d_mem_offsets, gcsa2_mem* d_mems, uint64_t mem_capacity,
+                          uint64_t* total_mems, uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  CHECK_INDEX(ix);
+  if(total_mems == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total_mems = 0;
+  *total_hits = 0;
+  if(d_mem_offsets == nullptr || d_hit_offsets == nullptr || (d_offsets == nullptr && nq > 0) || (d_mems == nullptr && mem_capacity > 0) ||
+     (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = mem_hits_checks(ix, min_length, over);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(nq == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_mem_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  return mem_hits_core(ix, d_patterns, d_offsets, nq, total_pattern_bytes, min_length, hit_max, over, d_mem_offsets, d_mems, mem_capacity,
+                       total_mems, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_mem_hits_device: ") + e.what()); }
+}
+
+// The host form: pieces of tune.ms_piece_bytes pattern bytes (a batch of two pieces' worth or more; one piece otherwise), each
+// copied in, run through gcsa2_mem_hits_device and copied out behind the pieces before it.  A piece's device buffers are sized
+// from the caller's remaining room (one piece) or an estimate (a piece that needs more runs again with the exact sizes); once
+// the caller's room is exceeded the remaining pieces only count.
+int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                         uint64_t hit_max, int over, uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
+                         uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
+{
+  CHECK_INDEX(ix);
+  if(total_mems == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total_mems = 0;
+  *total_hits = 0;
+  if(mem_offsets == nullptr || hit_offsets == nullptr || (offsets == nullptr && nq > 0) || (mems == nullptr && mem_capacity > 0) ||
+     (hits == nullptr && hit_capacity > 0) || (nq > 0 && patterns == nullptr && offsets[nq] > offsets[0]))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = mem_hits_checks(ix, min_length, over);
+  if(rc != GCSA2_OK) { return rc; }
+  if(nq == 0) { mem_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  if(offsets[0] != 0 || !offsets_ok(offsets, nq)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  std::vector<u64> cut(1, 0);
+  while(cut.back() < nq)
+  {
+    const u64 b = cut.back();
+    if(offsets[nq] < 2 * ix->tune.ms_piece_bytes) { cut.push_back(nq); break; }
+    u64 lo = b + 1, hi = nq;                               // largest e with offsets[e] - offsets[b] <= the piece size, at least one pattern
+    while(lo < hi) { const u64 mid = (lo + hi + 1) / 2; if(offsets[mid] - offsets[b] <= ix->tune.ms_piece_bytes) { lo = mid; } else { hi = mid - 1; } }
+    cut.push_back(lo);
+  }
+  const u64 pieces = cut.size() - 1;
+  struct Dev
+  {
+    void* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void release() { for(void*& x : p) { if(x) { (void)hipFree(x); x = nullptr; } } }
+    ~Dev() { release(); }
+  } dev;
+  u64 mbase = 0, hbase = 0;
+  bool exceeded = false;
+  std::vector<u64> local;
+  for(u64 c = 0; c < pieces; c++)
+  {
+    const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+    local.resize(count + 1);
+    for(u64 i = 0; i <= count; i++) { local[i] = offsets[b + i] - first; }
+    const u64 mem_room = exceeded ? 0 : mem_capacity - mbase, hit_room = exceeded ? 0 : hit_capacity - hbase;
+    u64 rm = std::min(mem_room, pieces == 1 ? bytes + count : bytes / 8 + count + 1);
+    u64 rh = (pieces == 1 ? hit_room : std::min(hit_room, 16 * rm));
+    u64 m = 0, h = 0;
+    for(int attempt = 0; attempt < 2; attempt++)
+    {
+      dev.release();
+      HIP_TRY(hipMalloc(&dev.p[0], bytes + 16));
+      HIP_TRY(hipMalloc(&dev.p[1], (count + 1) * sizeof(u64)));
+      HIP_TRY(hipMalloc(&dev.p[2], (count + 1) * sizeof(u64)));
+      HIP_TRY(hipMalloc(&dev.p[3], std::max<u64>(rm, 1) * sizeof(gcsa2_mem)));
+      HIP_TRY(hipMalloc(&dev.p[4], (rm + 1) * sizeof(u64)));
+      HIP_TRY(hipMalloc(&dev.p[5], std::max<u64>(rh, 1) * sizeof(u64)));
+      if(bytes > 0) { HIP_TRY(hipMemcpy(dev.p[0], patterns + first, bytes, hipMemcpyHostToDevice)); }
+      HIP_TRY(hipMemcpy(dev.p[1], local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice));
+      rc = gcsa2_mem_hits_device(ix, static_cast<const u8*>(dev.p[0]), static_cast<const u64*>(dev.p[1]), count, bytes, min_length, hit_max, over,
+                                 static_cast<u64*>(dev.p[2]), static_cast<gcsa2_mem*>(dev.p[3]), rm, &m, static_cast<u64*>(dev.p[4]),
+                                 static_cast<u64*>(dev.p[5]), rh, &h, nullptr);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && m <= mem_room && h <= hit_room && (m > rm || h > rh)) { rm = m; rh = h; continue; }
+      break;
+    }
+    if(rc == GCSA2_ERR_BUFFER_TOO_SMALL) { exceeded = true; }
+    else if(rc != GCSA2_OK) { return rc; }
+    else if(!exceeded)
+    {
+      HIP_TRY(hipMemcpy(local.data(), dev.p[2], (count + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+      for(u64 i = 0; i <= count; i++) { mem_offsets[b + i] = local[i] + mbase; }
+      if(m > 0) { HIP_TRY(hipMemcpy(mems + mbase, dev.p[3], m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
+      local.resize(m + 1);
+      HIP_TRY(hipMemcpy(local.data(), dev.p[4], (m + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+      for(u64 i = 0; i <= m; i++) { hit_offsets[mbase + i] = local[i] + hbase; }
+      if(h > 0) { HIP_TRY(hipMemcpy(hits + hbase, dev.p[5], h * sizeof(u64), hipMemcpyDeviceToHost)); }
+    }
+    mbase += m;
+    hbase += h;
+  }
+  *total_mems = mbase;
+  *total_hits = hbase;
+  if(exceeded || mbase > mem_capacity || hbase > hit_capacity)
+  {
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, mbase > mem_capacity ? "MEM buffer too small" : "hit buffer too small");
+  }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_mem_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"

@@ -185,6 +185,40 @@ public:
     breaks.resize(total);
   }
 
+  // A MEM finder's seeds in one call (gcsa2_mem_hits_batch): the MEMs of match_breaks_batch with count(range), and for each
+  // MEM its locate(range) values when hit_max == 0 or count <= hit_max; above the cap none (sample == false) or
+  // locate(range, hit_max) (sample == true).  MEMs of pattern q: [mem_offsets[q], mem_offsets[q + 1]); hits of MEM i:
+  // [hit_offsets[i], hit_offsets[i + 1]).
+  void mem_hits_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type min_length,
+                      size_type hit_max, bool sample, std::vector<size_type>& mem_offsets, std::vector<gcsa2_mem>& mems,
+                      std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
+    const size_type nq = offsets.empty() ? 0 : offsets.size() - 1;
+    mem_offsets.assign(nq + 1, 0);
+    mems.assign(4 * nq + 16, gcsa2_mem());
+    hits.resize(16 * nq + 64);
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total_mems = 0, total_hits = 0;
+    for(int attempt = 0; attempt < 2; attempt++)
+    {
+      hit_offsets.assign(mems.size() + 1, 0);
+      const int rc = gcsa2_mem_hits_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), nq,
+                                          min_length, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, mem_offsets.data(), mems.data(),
+                                          mems.size(), &total_mems, hit_offsets.data(), hits.data(), hits.size(), &total_hits);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0)
+      {
+        if(total_mems > mems.size()) { mems.assign(total_mems, gcsa2_mem()); }
+        if(total_hits > hits.size()) { hits.resize(total_hits); }
+        continue;
+      }
+      check(rc, "GCSA::mem_hits_batch()");
+      break;
+    }
+    mems.resize(total_mems);
+    hit_offsets.resize(total_mems + 1);
+    hits.resize(total_hits);
+  }
+
   // Memory pressure (gcsa2_index_set_tables / gcsa2_index_trim): drop (0), build (1) or leave (-1) the pair blocks and the
   // locate table, resize the seed table (kmer_k: -1 leaves it, 0 drops it); give back staging and scratch memory.  Results
   // never change.  Not to be called while queries run on this index or on copies of it (copies share the device image).

@@ -443,6 +443,35 @@ int gcsa2_match_breaks_device(const gcsa2_index* index, const uint8_t* d_pattern
 int gcsa2_match_breaks_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
                              uint64_t min_length, uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity,
                              uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks);
+/* MEM hits: the break records of gcsa2_match_breaks_device with count() and their positions, a MEM finder's seeds in one
+ * call.  MEMs of pattern q: d_mems[d_mem_offsets[q] .. d_mem_offsets[q + 1]), exactly the records gcsa2_match_breaks_device
+ * returns for min_length (min_length >= 1, GCSA2_ERR_INVALID_ARGUMENT otherwise), in the same order, each with
+ * count = GCSA::count(sp, ep).  Hits of MEM i: d_hits[d_hit_offsets[i] .. d_hit_offsets[i + 1]):
+ *   count == 0: none;
+ *   hit_max == 0 (no cap) or count <= hit_max: the sorted distinct values of gcsa2_locate_into(sort = 1);
+ *   otherwise, over == GCSA2_MEM_OVER_SKIP: none (the MEM and its count are still reported);
+ *   otherwise, over == GCSA2_MEM_OVER_SAMPLE: the values of gcsa2_locate_max(range, hit_max), value for value and in order
+ *   (src/gcsa.cpp:844-878); its INVALID_ARGUMENT for a range the reference would draw forever on is passed through.
+ * d_mem_offsets: n_queries + 1 entries; d_hit_offsets: mem_capacity + 1.  *total_mems and *total_hits are always the sizes
+ * needed; if either exceeds its capacity the call fails with GCSA2_ERR_BUFFER_TOO_SMALL and writes nothing into d_mems,
+ * d_hit_offsets or d_hits.  Nothing is ever written behind d_mems + mem_capacity or d_hits + hit_capacity.  Needs the LCP
+ * array, the samples and the counters (GCSA2_ERR_MISSING_COMPONENT).  total_pattern_bytes = d_offsets[n_queries] or
+ * GCSA2_UNKNOWN (read back).  Enqueued on `stream`, complete on return. */
+typedef struct gcsa2_mem { uint64_t position, length, sp, ep, count; } gcsa2_mem;
+#define GCSA2_MEM_OVER_SKIP   0   /* count > hit_max: record the MEM and its count, no hits      */
+#define GCSA2_MEM_OVER_SAMPLE 1   /* count > hit_max: hits = locate(range, hit_max) (gcsa.cpp:844-878) */
+int gcsa2_mem_hits_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_queries,
+                          uint64_t total_pattern_bytes, uint64_t min_length, uint64_t hit_max, int over,
+                          uint64_t* d_mem_offsets, gcsa2_mem* d_mems, uint64_t mem_capacity, uint64_t* total_mems,
+                          uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+/* The same for a batch in host memory (offsets[0] == 0): copies in, runs, copies out.  A batch of two pieces' worth of pattern
+ * bytes or more (32 MB pieces, as gcsa2_match_breaks_batch) goes in pieces whose MEMs and hits keep their order; a batch in one
+ * piece writes nothing into mems, hit_offsets or hits on GCSA2_ERR_BUFFER_TOO_SMALL, one in pieces leaves their contents
+ * unspecified then.  Complete on return. */
+int gcsa2_mem_hits_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
+                         uint64_t min_length, uint64_t hit_max, int over,
+                         uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
+                         uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
