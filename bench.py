@@ -11,7 +11,12 @@ ncclRecv over xGMI; u64 pairs on the wire, the path nodes do not fit 32 bits).  
 path (gcsa2_find_device, kernel k_find2) over the rank's shard, inputs resident in HBM, + that gather.
 Prints ONE JSON line on rank 0 (contract: task statement / DESIGN.md section 5).
 
-At N = 1 the same run also measures, as secondary objects of that line (never part of `value`):
+A plain run does only what the headline needs: it builds the find() image, warms up, times the steps, writes --dump-outputs
+and prints the line.  Everything else runs with `--full` only: the closed-form check of the ranges, the instrumented twin
+behind `roofline` and the config's per-query figures, the request-rate ceiling, `cpu_baseline`, the device telemetry, the
+host-batch and locate() legs, the secondaries below, the measured-traffic pass and, at N > 1, the gather timed alone.
+
+With `--full` at N = 1 the same run also measures, as secondary objects of that line (never part of `value`):
   config5  BASELINE configs[4]: 1 M 256-bp patterns on the same index, half of them with a substitution
            every 41 bp: find() with parent() on failure (fused matching statistics), then locate()
   chr22    BASELINE configs[1] and [2]: 10 M 32-mer find() and locate() on the chr22-like SNP graph
@@ -74,7 +79,7 @@ def parse():
     ap.add_argument("--secondary", choices=["all", "config5", "wide", "ladder", "chr22", "repeats", "repeats30", "human32", "human_snp"], default="all", help="N = 1: which secondary measurements to run")
     ap.add_argument("--pipeline-sweep", default="", help="diagnostic: lanes:chunk_log2[,...] -- the host-batch leg repeated per shape of the host pipeline (gcsa2_index_set_pipeline)")
     ap.add_argument("--locate-ranges", type=int, default=0, help="ranges of the locate() leg (default: 400 k on the repeat-rich indexes, every range on chr22)")
-    ap.add_argument("--locate", action="store_true", help="chr22 / repeats / repeats30: run the locate() leg even with --no-extras (profiler passes)")
+    ap.add_argument("--locate", action="store_true", help="--full, chr22 / repeats / repeats30: run the locate() leg even with --no-extras (profiler passes)")
     ap.add_argument("--variant", type=int, default=2, help="find launch shape (2 = one lane per query in batch order, 4 = queries ordered by length first)")
     ap.add_argument("--full-json", default="bench_full.json", help="where the full result object goes (every leg in full; the stdout line is the compact form)")
     ap.add_argument("--full-line", action="store_true", help="print the full object as the stdout line (profiles/; the driver needs the compact line)")
@@ -83,9 +88,14 @@ def parse():
     ap.add_argument("--gather-only", action="store_true", help="N > 1: time the gather alone (no kernel, no packing) after the timed steps -- on by default; this flag skips the secondaries instead")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the (sp, ep) ranges of the last step -- a fixed seeded "
                                                                       "sample of at most 2^21 queries -- to DIR/find_ranges.npy and the queries' ids to DIR/find_query_ids.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="run everything beyond the headline as well (module docstring); the options above that "
+                                                         "select or skip legs apply within a --full run")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                       # a plain run: the headline alone, on the find()-only image
+        args.no_cpu = args.no_secondary = args.no_extras = True
+        args.locate = False
     return args
 
 
@@ -798,7 +808,7 @@ def measure(args, D, dev, wl, steps, warmup):
         D.dist.all_gather_object(everyone, mine)
         per_rank = everyone
     gather_only = None
-    if D.active and steps > 0:
+    if D.active and steps > 0 and args.full:
         # The gather ALONE -- no kernel, no packing, no unpack: the blocks of the last steps once more --, back to back on the gather
         # stream: what the root's links take in per second, next to `gather_hidden_frac` (VERDICT r05 #6 ii).  Every rank takes part.
         reps = max(steps, 4)
@@ -833,6 +843,8 @@ def measure(args, D, dev, wl, steps, warmup):
             got = [int(part[:, 0].sum().item()), int(part[:, 1].sum().item())]
             assert got == per_rank[r]["shard_checksum"], f"the shard gathered from rank {r} differs from what that rank computed"
         result["gathered_shards_verified"] = len(bounds)
+    if not args.full:
+        return result
 
     # algorithmic traffic of one launch (instrumented kernel, outside the timed region)
     d_stats = torch.zeros(8, dtype=torch.int64, device=dev)
@@ -1098,7 +1110,7 @@ def measured_traffic(args, nq):
     out_dir = tempfile.mkdtemp(prefix="gcsa2_pmc_", dir="/tmp")
     cmd = [prof, "--kernel-include-regex", "k_find2", "--pmc", "TCC_EA0_RDREQ_32B_sum", "TCC_EA0_RDREQ_64B_sum", "TCC_EA0_RDREQ_128B_sum",
            "--output-format", "csv", "-d", out_dir, "-o", "x", "--",
-           sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary",
+           sys.executable, os.path.abspath(__file__), "--full", "--workload", args.workload, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary",
            "--no-extras", "--full-json", "", "--set", args.set, "--pattern-len", str(args.pattern_len), "--variant", str(args.variant),
            "--junctions", str(args.junctions), "--snp-period", str(args.snp_period), "--order", str(args.order), "--cache-dir", args.cache_dir]
     for flag, value in (("--degree", args.degree), ("--log2-bases", args.log2_bases), ("--queries", args.queries)):
@@ -1209,15 +1221,18 @@ def roofline(args, r, wl, key, ceiling=None):
 
 def find_config(wl, r, world):
     gpu = wl.gpu
-    return {"workload": wl.label, "path_nodes": int(wl.ix.n), "edges": int(wl.ix.e), "queries_total": wl.total_queries,
-            "queries_per_gpu": wl.nq, "pattern_len": wl.m, "index_bytes_hbm": gpu.device_bytes(),
-            "pair_block_bytes": gpu.pair_block_bytes(), "single_block_bytes": int(wl.ix.sigma) * (int(wl.ix.n) // 384 + 1) * 128,
-            "kmer_table_k": gpu.kmer_table_k(), "found": r["found"], "lf_steps_per_query": r["lf_steps"] / wl.nq,
-            "second_fetch_fraction_of_steps": r["second_fetches"] / max(r["fetch_steps"], 1), "wide_seed_entries_hit": r["wide_seeds"],
-            "blocks_per_query": r["blocks"] / wl.nq, "block_bytes": gpu.find_block_bytes(),
-            "parallelism": f"replicated index, contiguous query shards x{world}, one gather of ranges per step: {r['gather']}"
-                           + (" as 40-bit sp + length byte, 6 bytes (+ a list of the long ranges)" if r.get("pack48") else
-                              (" as (sp, len) u32 pairs" if r["pack32"] else (" as (sp, len) 40-bit pairs, 10 bytes" if r.get("pack40") else "")))}
+    cfg = {"workload": wl.label, "path_nodes": int(wl.ix.n), "edges": int(wl.ix.e), "queries_total": wl.total_queries,
+           "queries_per_gpu": wl.nq, "pattern_len": wl.m, "index_bytes_hbm": gpu.device_bytes(),
+           "pair_block_bytes": gpu.pair_block_bytes(), "single_block_bytes": int(wl.ix.sigma) * (int(wl.ix.n) // 384 + 1) * 128,
+           "kmer_table_k": gpu.kmer_table_k(), "block_bytes": gpu.find_block_bytes(),
+           "parallelism": f"replicated index, contiguous query shards x{world}, one gather of ranges per step: {r['gather']}"
+                          + (" as 40-bit sp + length byte, 6 bytes (+ a list of the long ranges)" if r.get("pack48") else
+                             (" as (sp, len) u32 pairs" if r["pack32"] else (" as (sp, len) 40-bit pairs, 10 bytes" if r.get("pack40") else "")))}
+    if "blocks" in r:                       # the instrumented twin ran (--full)
+        cfg.update({"found": r["found"], "lf_steps_per_query": r["lf_steps"] / wl.nq,
+                    "second_fetch_fraction_of_steps": r["second_fetches"] / max(r["fetch_steps"], 1), "wide_seed_entries_hit": r["wide_seeds"],
+                    "blocks_per_query": r["blocks"] / wl.nq})
+    return cfg
 
 
 # ---- N = 1 secondaries ---------------------------------------------------------------------------------------
@@ -2121,8 +2136,8 @@ def one_number(key, leg):
 
 
 def compact_line(full):
-    """The stdout line: the contract's keys, `roofline`, `cpu_baseline` and one number per secondary; everything else lives in
-    bench_full.json (and on stderr).  Kept under LINE_LIMIT bytes by construction, and by dropping secondaries if it is not."""
+    """The stdout line: the contract's keys and, from a --full run, `roofline`, `cpu_baseline` and one number per secondary; everything
+    else lives in bench_full.json (and on stderr).  Kept under LINE_LIMIT bytes by construction, and by dropping secondaries if it is not."""
     out = pick(full, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     cfg = dict(full["config"])
     for k in ("single_block_bytes", "block_bytes", "wide_seed_entries_hit", "found"):        # (in bench_full.json)
@@ -2130,12 +2145,13 @@ def compact_line(full):
     cfg["workload"] = short(cfg["workload"], 250)
     cfg["parallelism"] = short(cfg.get("parallelism", ""), 160)
     out["config"] = cfg
-    rf = dict(full["roofline"])
-    for k in ("working_set_note", "traffic_source_note", "traffic_GBps", "traffic_frac_of_measured_hbm_rate", "traffic_lookup", "requests_per_distinct_line"):
-        rf.pop(k, None)
-    if "request_rate" in rf:
-        rf["request_rate"] = {k: v for k, v in rf["request_rate"].items() if k != "ceiling_source"}
-    out["roofline"] = rf
+    if "roofline" in full:                  # (--full runs)
+        rf = dict(full["roofline"])
+        for k in ("working_set_note", "traffic_source_note", "traffic_GBps", "traffic_frac_of_measured_hbm_rate", "traffic_lookup", "requests_per_distinct_line"):
+            rf.pop(k, None)
+        if "request_rate" in rf:
+            rf["request_rate"] = {k: v for k, v in rf["request_rate"].items() if k != "ceiling_source"}
+        out["roofline"] = rf
     if "value_at_reference_footprint" in full:
         out["value_at_reference_footprint"] = {k: v for k, v in full["value_at_reference_footprint"].items() if k != "note"}
     if "cpu_baseline" in full:
@@ -2357,11 +2373,13 @@ def run_legs(args, D, dev, local_rank, wl, ceiling, emitter):
     import torch
     rank, world = D.rank, D.world
     r = measure(args, D, dev, wl, args.steps, args.warmup)
-    # every rank checks its own shard; the root also checks everything it gathered
-    ok = wl.verify(r["d_out"], wl.first, wl.nq)
-    if rank == 0 and r["gathered"] is not None and ok is not None:
-        ok = ok and wl.verify(r["gathered"], 0, wl.total_queries)
-    checked = None if ok is None else D.all_true(ok)
+    checked = None
+    if args.full:
+        # every rank checks its own shard; the root also checks everything it gathered
+        ok = wl.verify(r["d_out"], wl.first, wl.nq)
+        if rank == 0 and r["gathered"] is not None and ok is not None:
+            ok = ok and wl.verify(r["gathered"], 0, wl.total_queries)
+        checked = None if ok is None else D.all_true(ok)
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, r["gathered"] if r["gathered"] is not None else r["d_out"])
 
@@ -2374,8 +2392,9 @@ def run_legs(args, D, dev, local_rank, wl, ceiling, emitter):
             "ms_per_step": r["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": wl.scaling,
             "vs_baseline": None, "dtype": "u64", "data": "synthetic",
             "config": find_config(wl, r, world),
-            "roofline": roofline(args, r, wl, f"{args.workload}_{size}_{wl.m}_{args.set}"),
         }
+        if args.full:
+            result["roofline"] = roofline(args, r, wl, f"{args.workload}_{size}_{wl.m}_{args.set}")
         result["config"]["pattern_set"] = args.set
         if r["per_rank"] is not None:
             ranks = r["per_rank"]
@@ -2407,7 +2426,8 @@ def run_legs(args, D, dev, local_rank, wl, ceiling, emitter):
             if problems:
                 mg["problems"] = problems
                 emitter.exit_code = 3
-        result["config"]["all_ranges_equal_closed_form"] = checked
+        if args.full:
+            result["config"]["all_ranges_equal_closed_form"] = checked
         if ceiling is not None:
             result["roofline"]["request_rate"]["ceiling_source"] = "gather_bench --mode lds128 35 on this box, before the index was loaded"
     emitter.headline(result)

@@ -50,7 +50,8 @@ def check_compact(line, full):
     return c
 
 
-def run(cmd, env=None, timeout=900, tmp=None):
+def run_line(cmd, env=None, timeout=900):
+    """(stdout line, full object) of one bench.py run that must succeed."""
     import tempfile
     full_env = dict(os.environ)
     full_env.update(env or {})
@@ -62,7 +63,13 @@ def run(cmd, env=None, timeout=900, tmp=None):
         assert len(lines) == 1, out.stdout[-2000:]
         with open(path) as f:
             full = strict(f.read())
-    full["_line"] = check_compact(lines[0], full)
+    return lines[0], full
+
+
+def run(cmd, env=None, timeout=900, tmp=None):
+    """A --full run: the headline with its roofline and closed-form check, and the legs the command selects."""
+    line, full = run_line(cmd + ["--full"], env=env, timeout=timeout)
+    full["_line"] = check_compact(line, full)
     return full
 
 
@@ -77,6 +84,37 @@ def check_line(d, gpus, steps):
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert r["kernel_ms"] * d["steps"] <= d["ms_per_step"] * d["steps"] * 1.02 + 0.5
     assert d["config"]["all_ranges_equal_closed_form"] is True
+
+
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "full_json"}
+
+
+@pytest.mark.parametrize("ranks", [1, 2], ids=["one-gpu", "two-ranks-through-the-host"])
+def test_a_plain_run_is_the_headline_alone(ranks, tmp_path):
+    """Without --full a run sets up, warms up, times the steps, dumps the last step's ranges and prints the line: no roofline, no
+    closed-form check, no legs.  It times the batch of a --full run and hands back the same ranges, which that run checked
+    against the closed form."""
+    import numpy as np
+    cmd = [sys.executable, "bench.py", "--gpus", str(ranks), "--degree", "20", "--queries", "300001", "--steps", "3", "--warmup", "1"]
+    env = {"GCSA2_BENCH_BACKEND": "gloo"} if ranks > 1 else {}
+    line, full = run_line(cmd + ["--dump-outputs", str(tmp_path / "plain")], env=env)
+    c = strict(line)
+    assert len(line) < LINE_LIMIT and c["secondary"] == {} and "roofline" not in c and "cpu_baseline" not in c
+    assert c["value"] == full["value"] and c["ms_per_step"] == full["ms_per_step"]
+    assert c["metric"] == "kmer_find_queries_per_sec" and c["unit"] == "queries/s" and c["higher_is_better"] is True and c["dtype"] == "u64"
+    assert c["n_gpus"] == ranks and c["steps"] == 3 and c["warmup"] == 1 and c["value"] > 0
+    assert abs(c["value"] - 300001 * 3 / (c["ms_per_step"] * 3e-3)) < 1e-6 * c["value"]
+    assert set(full) == PLAIN_KEYS | ({"multi_gpu"} if ranks > 1 else set())
+    assert c["config"]["queries_total"] == 300001 and "all_ranges_equal_closed_form" not in c["config"]
+    if ranks > 1:
+        mg = full["multi_gpu"]
+        assert mg["asserted"] is True and mg["gathered_shards_verified"] == 2 and mg["gather_only"] is None
+    d = run(cmd + ["--no-cpu", "--no-secondary", "--dump-outputs", str(tmp_path / "full")], env=env)
+    check_line(d, ranks, 3)
+    for name in ("find_ranges.npy", "find_query_ids.npy"):
+        plain, checked = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert plain.dtype == np.float64 and plain.shape[0] == 300001 and np.array_equal(plain, checked), name
 
 
 def test_single_gpu_line_with_secondaries():

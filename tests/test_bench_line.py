@@ -119,3 +119,38 @@ def test_locate_counter_summary_adds_up(tmp_path):
     d = json.loads(out.stdout)
     assert d["read_bytes_per_call"] == (128 * 1500 + 64 * 10 + 32 * 4) / 5 and d["write_bytes_per_call"] == (64 * 200 + 32 * 100) / 5
     assert d["read_requests_per_call"] == 1514 / 5 and d["write_requests_per_call"] == 60 and "k_over_split" in out.stderr
+
+
+def test_a_plain_run_gives_a_line_without_roofline_or_legs():
+    """A run without --full has the headline alone: no roofline, no closed-form check, no legs -- the line carries the contract's
+    keys, the config and an empty `secondary`."""
+    import bench
+    full = load_full()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config", "full_json")}
+    plain["config"] = {k: v for k, v in full["config"].items()
+                       if k not in ("found", "lf_steps_per_query", "second_fetch_fraction_of_steps", "wide_seed_entries_hit", "blocks_per_query",
+                                    "all_ranges_equal_closed_form")}
+    line = bench.compact_line(bench.finite(plain))
+    assert len(line) < bench.LINE_LIMIT and "\n" not in line
+    c = strict(line)
+    assert c["value"] == full["value"] and c["ms_per_step"] == full["ms_per_step"] and c["metric"] == "kmer_find_queries_per_sec"
+    assert c["unit"] == "queries/s" and c["higher_is_better"] is True and c["dtype"] == "u64"
+    assert "roofline" not in c and "cpu_baseline" not in c and c["secondary"] == {} and "secondary_dropped_for_size" not in c
+    assert c["config"]["path_nodes"] == full["config"]["path_nodes"] and "single_block_bytes" not in c["config"]
+
+
+def test_plain_and_full_runs_parse_the_same_options():
+    """--full is off by default; without it the leg switches are set as for the headline alone."""
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "3", "--warmup", "1"]
+        plain = bench.parse()
+        sys.argv = ["bench.py", "--steps", "3", "--warmup", "1", "--full", "--locate"]
+        full = bench.parse()
+    finally:
+        sys.argv = argv
+    assert not plain.full and plain.no_cpu and plain.no_secondary and plain.no_extras and not plain.locate
+    assert full.full and not full.no_cpu and not full.no_secondary and not full.no_extras and full.locate
+    assert (plain.steps, plain.warmup, plain.gpus, plain.workload) == (full.steps, full.warmup, full.gpus, full.workload) == (3, 1, 1, "pangenome")

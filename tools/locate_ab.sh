@@ -14,7 +14,7 @@ ONLY="--kernel-include-regex k_locate_|k_over_|k_sort_|k_compact|k_mark_|k_dedup
 for m in 16 32; do
   if [ $m = 16 ]; then R=100000; else R=400000; fi
   timeout ${PASS_TIMEOUT:-900} rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/gpurun_out/${TAG}_$m -o x -- \
-    python $ROOT/bench.py --workload repeats30 --pattern-len $m --locate-ranges $R --locate --steps 5 --warmup 1 --no-cpu --no-secondary --no-extras \
+    python $ROOT/bench.py --full --workload repeats30 --pattern-len $m --locate-ranges $R --locate --steps 5 --warmup 1 --no-cpu --no-secondary --no-extras \
       --full-json $ROOT/gpurun_out/${TAG}_$m.json > $ROOT/gpurun_out/${TAG}_$m.log 2>&1
   python - <<PY
 import csv, glob

@@ -13,7 +13,7 @@ PASSES=${PASSES:-rdreq l2 fetch trace}      # e.g. PASSES="rdreq trace" for swee
 ROOT=$(pwd)
 cd /tmp && export TMPDIR=/tmp
 for WL in $WORKLOADS; do
-  CMD="python $ROOT/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu --no-secondary --no-extras $EXTRA"
+  CMD="python $ROOT/bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu --no-secondary --no-extras $EXTRA"
   ONLY="--kernel-include-regex k_find2"      # counters for the find kernels only (collecting them for every torch kernel of the generator is slow, and crashed once)
   for P in $PASSES; do
     case $P in

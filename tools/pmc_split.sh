@@ -5,7 +5,7 @@
 set -u
 TAG=$1; M=$2; R=$3
 ROOT=$(pwd); cd /tmp; export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --workload repeats30 --pattern-len $M --locate-ranges $R --locate --steps 2 --warmup 1 --no-cpu --no-secondary --no-extras --no-measured-traffic --full-json /tmp/pmc_split_full.json"
+CMD="python $ROOT/bench.py --full --workload repeats30 --pattern-len $M --locate-ranges $R --locate --steps 2 --warmup 1 --no-cpu --no-secondary --no-extras --no-measured-traffic --full-json /tmp/pmc_split_full.json"
 ONLY="--kernel-include-regex k_over_split|k_sort_bucket"
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU"; do
   name=$(echo $set | cut -d' ' -f1)
