@@ -39,7 +39,7 @@ EXPORTS = [
     "gcsa2_group_find_batch", "gcsa2_group_find_device", "gcsa2_group_uses_rccl",
     "gcsa2_group_match_stats_device", "gcsa2_group_locate_device", "gcsa2_comm_match_stats", "gcsa2_comm_locate",
     "gcsa2_comm_unique_id", "gcsa2_comm_create", "gcsa2_comm_create_custom", "gcsa2_comm_destroy", "gcsa2_comm_rank", "gcsa2_comm_world", "gcsa2_comm_rccl_ranks", "gcsa2_comm_gather",
-    "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch",
+    "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -151,6 +151,8 @@ def load_library():
     L.gcsa2_match_breaks_device.argtypes = [vp, vp, vp, u64, u64, i32, u64, vp, vp, u64, u64p, vp, vp, vp]
     L.gcsa2_mem_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_sub_mem_hits_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
+    L.gcsa2_sub_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64p, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
     L.gcsa2_group_destroy.argtypes = [vp]
     L.gcsa2_group_destroy.restype = None
@@ -679,6 +681,70 @@ class GCSA:
             err.needed = (total_m.value, total_h.value)
             raise err
         return total_m.value, total_h.value
+
+    def sub_mem_hits_batch(self, patterns, offsets, mem_offsets, mems, min_length, reseed_length, hit_max=0, sample=False, out=None):
+        """Sub-MEM reseeding of a batch in host memory (gcsa2_sub_mem_hits_batch): inside every MEM (rows of `mems`, five u64
+        {position, length, sp, ep, count} as mem_hits_batch returns them, per pattern by `mem_offsets`) of at least
+        reseed_length bases, the matches of at least min_length that occur more often than the MEM.  Returns (sub_offsets
+        (MEMs + 1), subs (total, 5), hit_offsets (total + 1), hits); hits follow mem_hits_batch's rules.  The buffers are grown
+        from the refusal.  `out` = (sub_offsets, subs, hit_offsets, hits) arrays of the caller; too small ones raise
+        BUFFER_TOO_SMALL with `needed` = (sub-MEMs, hits)."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        mem_offsets = np.ascontiguousarray(mem_offsets, dtype=np.uint64)
+        mems = np.ascontiguousarray(mems, dtype=np.uint64).reshape(-1, 5)
+        nq, nm = offsets.shape[0] - 1, mems.shape[0]
+        over = 1 if sample else 0
+        total_s, total_h = C.c_uint64(), C.c_uint64()
+
+        def call(soff, subs, hoff, hits):
+            assert soff.dtype == np.uint64 and soff.shape[0] >= nm + 1 and subs.dtype == np.uint64 and subs.flags.c_contiguous
+            assert subs.shape[1] == 5 and hoff.dtype == np.uint64 and hoff.shape[0] >= subs.shape[0] + 1 and hits.dtype == np.uint64
+            return self._L.gcsa2_sub_mem_hits_batch(self._h, _p8(patterns), _p64(offsets), nq, _p64(mem_offsets), mems.ctypes.data, nm,
+                                                    int(min_length), int(reseed_length), int(hit_max), over, soff.ctypes.data, subs.ctypes.data,
+                                                    subs.shape[0], C.byref(total_s), hoff.ctypes.data, hits.ctypes.data, hits.shape[0],
+                                                    C.byref(total_h))
+
+        if out is not None:
+            soff, subs, hoff, hits = out
+            rc = call(soff, subs, hoff, hits)
+        else:
+            scap, hcap = 4 * nm + 16, 16 * nm + 64
+            soff = np.zeros(nm + 1, dtype=np.uint64)
+            for _ in range(2):
+                subs = np.zeros((scap, 5), dtype=np.uint64)
+                hoff = np.zeros(scap + 1, dtype=np.uint64)
+                hits = np.zeros(hcap, dtype=np.uint64)
+                rc = call(soff, subs, hoff, hits)
+                if rc != STATUS_BUFFER_TOO_SMALL:
+                    break
+                scap, hcap = max(scap, total_s.value), max(hcap, total_h.value)
+        if rc == STATUS_BUFFER_TOO_SMALL:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_s.value, total_h.value)
+            raise err
+        _check(rc)
+        s, h = total_s.value, total_h.value
+        return soff[: nm + 1], subs[:s], hoff[: s + 1], hits[:h]
+
+    def sub_mem_hits_device(self, d_patterns, d_offsets, nq, total_bytes, d_mem_offsets, d_mems, n_mems, min_length, reseed_length, hit_max,
+                            sample, d_sub_offsets, d_subs, sub_capacity, d_hit_offsets, d_hits, hit_capacity, stream=0):
+        """Sub-MEM reseeding into caller-owned device buffers (gcsa2_sub_mem_hits_device): d_mems holds n_mems records of five
+        u64 (None = read d_mem_offsets[nq]), d_sub_offsets n_mems + 1 entries, d_subs sub_capacity records, d_hit_offsets
+        sub_capacity + 1 entries, d_hits hit_capacity values.  Returns (sub-MEMs, hits); raises Gcsa2Error (BUFFER_TOO_SMALL,
+        `.needed` = (sub-MEMs, hits)) when a buffer is too small."""
+        total_s, total_h = C.c_uint64(), C.c_uint64()
+        tb = 0xFFFFFFFFFFFFFFFF if total_bytes is None else int(total_bytes)
+        nm = 0xFFFFFFFFFFFFFFFF if n_mems is None else int(n_mems)
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        rc = self._L.gcsa2_sub_mem_hits_device(self._h, d_patterns, d_offsets, nq, tb, d_mem_offsets, d_mems, nm, int(min_length),
+                                               int(reseed_length), int(hit_max), over, d_sub_offsets, d_subs, sub_capacity, C.byref(total_s),
+                                               d_hit_offsets, d_hits, hit_capacity, C.byref(total_h), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_s.value, total_h.value)
+            raise err
+        return total_s.value, total_h.value
 
     def match_stats_profile_device(self, d_patterns, d_offsets, nq, total_bytes, d_ms, d_ranges, d_fallbacks, d_prof, stream=0):
         """Diagnostic: the instrumented matching-statistics kernel (cycles per phase and event counts into d_prof[16])."""

@@ -48,6 +48,7 @@ using namespace g2;
 #include "kernels_locate_max.hpp"
 #include "kernels_mem.hpp"
 #include "kernels_lcp.hpp"
+#include "kernels_submem.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -4763,6 +4764,9 @@ int mem_sampled(const gcsa2_index* ix, const u64* d_ranges, u64 ns, u64 hit_max,
   return GCSA2_OK;
 }
 
+int mem_hits_tail(const gcsa2_index* ix, const u64* brk, const u64* known, u64 m, u64 hit_max, int over, gcsa2_mem* d_mems, u64 mem_capacity,
+                  u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, Scratch& scratch, hipStream_t st);
+
 // gcsa2_mem_hits_device after its argument checks (nq > 0).  Host round trips: the pattern bytes (only when the caller does
 // not know them), the break total (inside gcsa2_match_breaks_device), the class totals, those of the locate passes, the end.
 int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 nq, u64 total_bytes, u64 min_length,
@@ -4802,6 +4806,17 @@ int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64
     scratch.settled = true;
     return GCSA2_OK;
   }
+  return mem_hits_tail(ix, brk, nullptr, m, hit_max, over, d_mems, mem_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
+}
+
+// Steps 2 onward of a MEM hits call, shared by mem_hits_core and sub_mem_hits_core: m (1 <= m < 2^32) records {position,
+// length, sp, ep} in device memory, with their count()s in `known` or (nullptr) computed here, become the caller's gcsa2_mem
+// records and their hit CSR.  *total_hits is always set; BUFFER_TOO_SMALL (m > mem_capacity or hits > hit_capacity) writes
+// nothing of the caller's.
+int mem_hits_tail(const gcsa2_index* ix, const u64* brk, const u64* known, u64 m, u64 hit_max, int over, gcsa2_mem* d_mems, u64 mem_capacity,
+                  u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, Scratch& scratch, hipStream_t st)
+{
+  int rc = GCSA2_OK;
   // 2. count() and the class of every MEM, one scan for the positions in both range lists and the full class's count() sum
   u64 *mems = nullptr, *full = nullptr, *sampled = nullptr, *full_off = nullptr, *full_val = nullptr, *samp_off = nullptr, *samp_val = nullptr;
   MemScan *words = nullptr, *pos = nullptr;
@@ -4809,7 +4824,7 @@ int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64
   HIP_TRY(scratch.get(mems, 5 * m));
   HIP_TRY(scratch.get(words, m + 1));
   HIP_TRY(scratch.get(pos, m + 1));
-  hipLaunchKernelGGL(k_mem_classify, dim3(grid_for(m + 1)), dim3(TPB), 0, st, ix->img, brk, m, hit_max, int(over == GCSA2_MEM_OVER_SAMPLE), mems, words);
+  hipLaunchKernelGGL(k_mem_classify, dim3(grid_for(m + 1)), dim3(TPB), 0, st, ix->img, brk, known, m, hit_max, int(over == GCSA2_MEM_OVER_SAMPLE), mems, words);
   LAUNCH_CHECK("k_mem_classify");
   size_t scan_bytes = 0;
   HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, scan_bytes, words, pos, MemScanOp(), MemScan{0, 0}, size_t(m + 1), st));
@@ -5014,6 +5029,197 @@ int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const u
   }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_mem_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== sub-MEM reseeding: the shorter, more frequent matches inside long MEMs, with count() and locate() (kernels_submem.hpp) =====
+namespace {
+
+// gcsa2_sub_mem_hits_device after its argument checks (nq > 0, 0 < n_mems < 2^32).  Host round trips: the control words
+// (bounds check, reseeded MEMs), the sub-MEM total with the overrun flag, those of the shared tail, the end.
+int sub_mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 nq, const u64* d_mem_offsets,
+                      const gcsa2_mem* d_mems, u64 n_mems, u64 min_length, u64 reseed_length, u64 hit_max, int over, u64* d_sub_offsets,
+                      gcsa2_mem* d_subs, u64 sub_capacity, u64* total_subs, u64* d_hit_offsets, u64* d_hits, u64 hit_capacity,
+                      u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  const u64* mems = reinterpret_cast<const u64*>(d_mems);
+  unsigned long long* ctl = nullptr;
+  u64 *pid = nullptr, *sizes = nullptr, *sub_off = nullptr;
+  u8* flag = nullptr;
+  u32* work = nullptr;
+  HIP_TRY(scratch.get(ctl, SUBMEM_CTL_WORDS));
+  HIP_TRY(scratch.get(pid, n_mems));
+  HIP_TRY(scratch.get(flag, n_mems));
+  HIP_TRY(scratch.get(work, n_mems));
+  HIP_TRY(scratch.get(sizes, n_mems + 1));
+  HIP_TRY(scratch.get(sub_off, n_mems + 1));
+  HIP_TRY(hipMemsetAsync(ctl, 0, SUBMEM_CTL_WORDS * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(sizes, 0, (n_mems + 1) * sizeof(u64), st));
+  // 1. each MEM's pattern, the bounds check, the list of reseeded MEMs
+  hipLaunchKernelGGL(k_submem_prep, dim3(grid_for(n_mems)), dim3(TPB), 0, st, d_offsets, nq, d_mem_offsets, mems, n_mems, reseed_length, pid, flag, ctl);
+  LAUNCH_CHECK("k_submem_prep");
+  size_t sel_bytes = 0;
+  hipcub::CountingInputIterator<u32> items(0);
+  HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, sel_bytes, items, flag, work, reinterpret_cast<u64*>(ctl + 2), size_t(n_mems), st));
+  char* sel_tmp = nullptr;
+  HIP_TRY(scratch.get(sel_tmp, sel_bytes));
+  HIP_TRY(hipcub::DeviceSelect::Flagged(sel_tmp, sel_bytes, items, flag, work, reinterpret_cast<u64*>(ctl + 2), size_t(n_mems), st));
+  unsigned long long words[SUBMEM_CTL_WORDS];
+  HIP_TRY(hipMemcpyAsync(words, ctl, sizeof(words), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if(words[0] != 0) { scratch.settled = true; return fail(GCSA2_ERR_INVALID_ARGUMENT, "sub_mem_hits: a MEM reaches beyond its pattern (position + length > pattern length)"); }
+  const u64 nr = (ix->img.n == 0 ? 0 : words[2]);
+  // 2. the walk, counting; the CSR offsets; the walk again, writing (persistent lanes: what the device holds at once)
+  const u64 resident = ix->tune.ms_grid != 0 ? ix->tune.ms_grid : u64(ix->compute_units) * 8;
+  const unsigned grid = unsigned(std::max<u64>(1, std::min<u64>((nr + TPB2 - 1) / TPB2, resident)));
+  if(nr > 0)
+  {
+    hipLaunchKernelGGL(k_submem_walk<false>, dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, mems, pid, work, nr, min_length, ctl,
+                       sizes, nullptr, nullptr, nullptr);
+    LAUNCH_CHECK("k_submem_walk<count>");
+  }
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, sub_off, size_t(n_mems + 1), st));
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, sub_off, size_t(n_mems + 1), st));
+  u64 s = 0;
+  HIP_TRY(hipMemcpyAsync(&s, sub_off + n_mems, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(words, ctl, sizeof(words), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if(words[1] != 0) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "sub_mem_hits: a walk did not shorten its match (parent() returned an lcp >= the match length); the index is inconsistent"); }
+  *total_subs = s;
+  if(s >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "sub_mem_hits: 2^32 or more sub-MEMs in one batch; split the batch"); }
+  if(s == 0)
+  {
+    HIP_TRY(hipMemcpyAsync(d_sub_offsets, sub_off, (n_mems + 1) * sizeof(u64), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    return GCSA2_OK;
+  }
+  u64 *recs = nullptr, *counts = nullptr;
+  HIP_TRY(scratch.get(recs, 4 * s));
+  HIP_TRY(scratch.get(counts, s));
+  HIP_TRY(hipMemsetAsync(ctl + 3, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_submem_walk<true>, dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, mems, pid, work, nr, min_length, ctl,
+                     nullptr, sub_off, recs, counts);
+  LAUNCH_CHECK("k_submem_walk<write>");
+  // 3. count class, locate, hits in sub-MEM order (mem_hits' tail); the offsets only once everything fits
+  const int rc = mem_hits_tail(ix, recs, counts, s, hit_max, over, d_subs, sub_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  scratch.settled = false;
+  HIP_TRY(hipMemcpyAsync(d_sub_offsets, sub_off, (n_mems + 1) * sizeof(u64), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_sub_mem_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_pattern_bytes,
+                              const uint64_t* d_mem_offsets, const gcsa2_mem* d_mems, uint64_t n_mems, uint64_t min_length, uint64_t reseed_length,
+                              uint64_t hit_max, int over, uint64_t* d_sub_offsets, gcsa2_mem* d_subs, uint64_t sub_capacity, uint64_t* total_subs,
+                              uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  (void)total_pattern_bytes;
+  CHECK_INDEX(ix);
+  if(total_subs == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total_subs = 0;
+  *total_hits = 0;
+  if(d_sub_offsets == nullptr || d_hit_offsets == nullptr || (nq > 0 && (d_offsets == nullptr || d_mem_offsets == nullptr)) ||
+     (d_subs == nullptr && sub_capacity > 0) || (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = mem_hits_checks(ix, min_length, over);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(nq > 0 && n_mems == GCSA2_UNKNOWN)
+  {
+    HIP_TRY(hipMemcpyAsync(&n_mems, d_mem_offsets + nq, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  if(nq == 0 || n_mems == 0 || n_mems == GCSA2_UNKNOWN)
+  {
+    HIP_TRY(hipMemsetAsync(d_sub_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  if(d_mems == nullptr || d_patterns == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  if(n_mems >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "sub_mem_hits: 2^32 or more MEMs in one batch; split the batch"); }
+  return sub_mem_hits_core(ix, d_patterns, d_offsets, nq, d_mem_offsets, d_mems, n_mems, min_length, reseed_length, hit_max, over, d_sub_offsets,
+                           d_subs, sub_capacity, total_subs, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_sub_mem_hits_device: ") + e.what()); }
+}
+
+// The host form, in one piece: patterns, offsets, MEM offsets and MEMs copied in, gcsa2_sub_mem_hits_device on buffers of the
+// caller's capacities, the results copied out.  The whole batch and both capacities must fit in device memory at once.
+int gcsa2_sub_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, const uint64_t* mem_offsets,
+                             const gcsa2_mem* mems, uint64_t n_mems, uint64_t min_length, uint64_t reseed_length, uint64_t hit_max, int over,
+                             uint64_t* sub_offsets, gcsa2_mem* subs, uint64_t sub_capacity, uint64_t* total_subs,
+                             uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
+{
+  CHECK_INDEX(ix);
+  if(total_subs == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  *total_subs = 0;
+  *total_hits = 0;
+  if(sub_offsets == nullptr || hit_offsets == nullptr || (nq > 0 && (offsets == nullptr || mem_offsets == nullptr)) ||
+     (subs == nullptr && sub_capacity > 0) || (hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  int rc = mem_hits_checks(ix, min_length, over);
+  if(rc != GCSA2_OK) { return rc; }
+  if(nq > 0 && n_mems == GCSA2_UNKNOWN) { n_mems = mem_offsets[nq]; }
+  if(nq == 0 || n_mems == 0) { sub_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  if(offsets[0] != 0 || !offsets_ok(offsets, nq)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(mem_offsets[0] != 0 || !offsets_ok(mem_offsets, nq) || mem_offsets[nq] != n_mems)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "MEM offsets must start at 0, be non-decreasing and end at n_mems");
+  }
+  if(mems == nullptr || (patterns == nullptr && offsets[nq] > 0)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  struct Dev
+  {
+    void* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~Dev() { for(void*& x : p) { if(x) { (void)hipFree(x); x = nullptr; } } }
+  } dev;
+  const u64 bytes = offsets[nq];
+  HIP_TRY(hipMalloc(&dev.p[0], bytes + 16));
+  HIP_TRY(hipMalloc(&dev.p[1], (nq + 1) * sizeof(u64)));
+  HIP_TRY(hipMalloc(&dev.p[2], (nq + 1) * sizeof(u64)));
+  HIP_TRY(hipMalloc(&dev.p[3], n_mems * sizeof(gcsa2_mem)));
+  HIP_TRY(hipMalloc(&dev.p[4], (n_mems + 1) * sizeof(u64)));
+  HIP_TRY(hipMalloc(&dev.p[5], std::max<u64>(sub_capacity, 1) * sizeof(gcsa2_mem)));
+  HIP_TRY(hipMalloc(&dev.p[6], (sub_capacity + 1) * sizeof(u64)));
+  HIP_TRY(hipMalloc(&dev.p[7], std::max<u64>(hit_capacity, 1) * sizeof(u64)));
+  if(bytes > 0) { HIP_TRY(hipMemcpy(dev.p[0], patterns, bytes, hipMemcpyHostToDevice)); }
+  HIP_TRY(hipMemcpy(dev.p[1], offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dev.p[2], mem_offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dev.p[3], mems, n_mems * sizeof(gcsa2_mem), hipMemcpyHostToDevice));
+  rc = gcsa2_sub_mem_hits_device(ix, static_cast<const u8*>(dev.p[0]), static_cast<const u64*>(dev.p[1]), nq, bytes, static_cast<const u64*>(dev.p[2]),
+                                 static_cast<const gcsa2_mem*>(dev.p[3]), n_mems, min_length, reseed_length, hit_max, over,
+                                 static_cast<u64*>(dev.p[4]), static_cast<gcsa2_mem*>(dev.p[5]), sub_capacity, total_subs,
+                                 static_cast<u64*>(dev.p[6]), static_cast<u64*>(dev.p[7]), hit_capacity, total_hits, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
+  const u64 s = *total_subs, h = *total_hits;
+  HIP_TRY(hipMemcpy(sub_offsets, dev.p[4], (n_mems + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+  if(s > 0) { HIP_TRY(hipMemcpy(subs, dev.p[5], s * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
+  HIP_TRY(hipMemcpy(hit_offsets, dev.p[6], (s + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+  if(h > 0) { HIP_TRY(hipMemcpy(hits, dev.p[7], h * sizeof(u64), hipMemcpyDeviceToHost)); }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_sub_mem_hits_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -28,16 +28,17 @@ struct MemScanOp
 
 // One lane per break record {position, length, sp, ep}; lane m writes the scan's closing zero.  The record becomes a
 // gcsa2_mem {position, length, sp, ep, count}; the class: count 0 -> none, hit_max 0 or count <= hit_max -> full,
-// otherwise sampled (sample != 0) or none.  A random 2-rank + 2-select gather per lane, like k_count.
-__global__ __launch_bounds__(TPB) void k_mem_classify(DevImage img, const u64* __restrict__ breaks, u64 m, u64 hit_max, int sample,
-                                                      u64* __restrict__ mems, MemScan* __restrict__ words)
+// otherwise sampled (sample != 0) or none.  A random 2-rank + 2-select gather per lane, like k_count; `known` (sub-MEMs, whose
+// walk computed every count) replaces the gather with counts[i].
+__global__ __launch_bounds__(TPB) void k_mem_classify(DevImage img, const u64* __restrict__ breaks, const u64* __restrict__ known, u64 m,
+                                                      u64 hit_max, int sample, u64* __restrict__ mems, MemScan* __restrict__ words)
 {
   const u64 i = u64(blockIdx.x) * TPB + threadIdx.x;
   if(i > m) { return; }
   if(i == m) { words[m] = MemScan{0, 0}; return; }
   const ulonglong2* src = reinterpret_cast<const ulonglong2*>(breaks + 4 * i);
   const ulonglong2 a = src[0], b = src[1];
-  const u64 count = count_range(img, b.x, b.y);
+  const u64 count = (known != nullptr ? known[i] : count_range(img, b.x, b.y));
   u64* dst = mems + 5 * i;
   dst[0] = a.x; dst[1] = a.y; dst[2] = b.x; dst[3] = b.y; dst[4] = count;
   MemScan w{0, 0};

@@ -219,6 +219,43 @@ public:
     hits.resize(total_hits);
   }
 
+  // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
+  // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
+  // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).
+  void sub_mem_hits_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets,
+                          const std::vector<size_type>& mem_offsets, const std::vector<gcsa2_mem>& mems, size_type min_length,
+                          size_type reseed_length, size_type hit_max, bool sample, std::vector<size_type>& sub_offsets,
+                          std::vector<gcsa2_mem>& subs, std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
+    const size_type nq = offsets.empty() ? 0 : offsets.size() - 1;
+    sub_offsets.assign(mems.size() + 1, 0);
+    subs.assign(4 * mems.size() + 16, gcsa2_mem());
+    hits.resize(16 * mems.size() + 64);
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total_subs = 0, total_hits = 0;
+    gcsa2_mem dummy_mem = gcsa2_mem();
+    for(int attempt = 0; attempt < 2; attempt++)
+    {
+      hit_offsets.assign(subs.size() + 1, 0);
+      const int rc = gcsa2_sub_mem_hits_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), nq,
+                                              mem_offsets.empty() ? &dummy_offset : mem_offsets.data(), mems.empty() ? &dummy_mem : mems.data(),
+                                              mems.size(), min_length, reseed_length, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP,
+                                              sub_offsets.data(), subs.data(), subs.size(), &total_subs, hit_offsets.data(), hits.data(), hits.size(),
+                                              &total_hits);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0)
+      {
+        if(total_subs > subs.size()) { subs.assign(total_subs, gcsa2_mem()); }
+        if(total_hits > hits.size()) { hits.resize(total_hits); }
+        continue;
+      }
+      check(rc, "GCSA::sub_mem_hits_batch()");
+      break;
+    }
+    subs.resize(total_subs);
+    hit_offsets.resize(total_subs + 1);
+    hits.resize(total_hits);
+  }
+
   // Memory pressure (gcsa2_index_set_tables / gcsa2_index_trim): drop (0), build (1) or leave (-1) the pair blocks and the
   // locate table, resize the seed table (kmer_k: -1 leaves it, 0 drops it); give back staging and scratch memory.  Results
   // never change.  Not to be called while queries run on this index or on copies of it (copies share the device image).

@@ -472,6 +472,54 @@ int gcsa2_mem_hits_batch(const gcsa2_index* index, const uint8_t* patterns, cons
                          uint64_t min_length, uint64_t hit_max, int over,
                          uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
                          uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* Sub-MEM reseeding: inside every MEM of at least reseed_length bases, the shorter matches that occur MORE OFTEN than the MEM
+ * (vg's GCSA mapper reseeds such MEMs: a long, nearly unique match may cross a SNP or come from a paralog), with count() and
+ * hits.  Input: the patterns and a MEM CSR as gcsa2_mem_hits_device returns it -- MEMs of pattern q are
+ * d_mems[d_mem_offsets[q] .. d_mem_offsets[q + 1]) (n_queries + 1 offsets; n_mems = d_mem_offsets[n_queries], or GCSA2_UNKNOWN:
+ * read back).  Of each MEM only {position b, length l, count c} are read.  A MEM with l < reseed_length gets no sub-MEMs;
+ * the sub-MEMs of the others are what this walk emits, in its order (descending position, as match_breaks lists breaks):
+ *
+ *   E = b + l;  x = e = E;  r = (0, n - 1)            r is the range of P[x .. e)
+ *   last_x = infinity
+ *   while e >= b + min_length:
+ *     if x > b:
+ *       r2 = LF(r, char2comp[P[x - 1]])
+ *       if r2 is not empty and count(r2) > c: x -= 1; r = r2; continue
+ *     the match ending at e cannot be extended -- candidate [x, e):
+ *     if e - x >= min_length and x < last_x: emit {x, e - x, r.sp, r.ep, count(r)}; last_x = x
+ *     if x == b: stop
+ *     if e == x: e -= 1; x = e; r = (0, n - 1); continue
+ *     p = parent(r);  e = x + p.lcp;  r = p.range         (LCPArray::parent)
+ *
+ * This is the LF + parent() interplay of the matching statistics, where a step also fails when count() drops to c or below,
+ * kept inside [b, E).  An emitted count is the one computed when the walk extended to that range (after a parent() jump x is
+ * unchanged, so nothing is emitted before the next successful step).  Meaning: count(find(.)) never drops when a match is
+ * shortened on the right, so while matches are no longer than the index's order the walk emits exactly the intervals [s, e)
+ * where s is the leftmost start with count(find(P[s' .. e))) > c for all s <= s' < e, of length >= min_length and not
+ * contained in one taken for a larger e -- the "backward search restarted at every end position" form of reseeding, in linear
+ * rather than quadratic time.  c = 0 gives the maximal matches inside the interval.
+ * Sub-MEMs of MEM k: d_subs[d_sub_offsets[k] .. d_sub_offsets[k + 1]) (n_mems + 1 offsets).  Hits of sub-MEM i:
+ * d_hits[d_hit_offsets[i] .. d_hit_offsets[i + 1]) (sub_capacity + 1 offsets), by the rules of gcsa2_mem_hits_device (hit_max,
+ * over).  *total_subs and *total_hits are always the sizes needed; if either exceeds its capacity the call fails with
+ * GCSA2_ERR_BUFFER_TOO_SMALL and writes nothing into d_sub_offsets, d_subs, d_hit_offsets or d_hits.  Nothing is ever written
+ * behind a capacity.  GCSA2_ERR_INVALID_ARGUMENT, with nothing written: min_length 0, an unknown `over`, a MEM with
+ * position + length beyond its pattern.  A walk that does not shorten its match (an inconsistent index) fails with
+ * GCSA2_ERR_HIP instead of spinning: a walk is bounded at 2 l + 2 rounds.  Needs the LCP array, the samples and the counters
+ * (GCSA2_ERR_MISSING_COMPONENT).  total_pattern_bytes is not needed (GCSA2_UNKNOWN is fine).  Fewer than 2^32 MEMs and
+ * sub-MEMs per call.  Enqueued on `stream`, complete on return. */
+int gcsa2_sub_mem_hits_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_queries,
+                              uint64_t total_pattern_bytes, const uint64_t* d_mem_offsets, const gcsa2_mem* d_mems, uint64_t n_mems,
+                              uint64_t min_length, uint64_t reseed_length, uint64_t hit_max, int over,
+                              uint64_t* d_sub_offsets, gcsa2_mem* d_subs, uint64_t sub_capacity, uint64_t* total_subs,
+                              uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+/* The same for a batch in host memory (offsets[0] == 0, mem_offsets[0] == 0, mem_offsets[n_queries] == n_mems or n_mems ==
+ * GCSA2_UNKNOWN): copies in, runs, copies out, in one piece -- the patterns, the MEMs and buffers of both capacities must fit
+ * in device memory at once.  Writes nothing on GCSA2_ERR_BUFFER_TOO_SMALL.  Complete on return. */
+int gcsa2_sub_mem_hits_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
+                             const uint64_t* mem_offsets, const gcsa2_mem* mems, uint64_t n_mems,
+                             uint64_t min_length, uint64_t reseed_length, uint64_t hit_max, int over,
+                             uint64_t* sub_offsets, gcsa2_mem* subs, uint64_t sub_capacity, uint64_t* total_subs,
+                             uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
