@@ -2,7 +2,8 @@
 // kernels + the C ABI of include/gcsa2_hip.h.  Written for CDNA4 only (wave64, no CUDA paths).
 //
 // One translation unit: the device code lives in kernels_*.hpp, this file holds the host side
-// (device image staging, handles, launches, the extern "C" entry points).
+// (device image staging, handles, launches, the extern "C" entry points); what carries a batch in host memory to the
+// kernels and back is in host_batch.hpp.
 //
 // Kernel <-> reference map (paths relative to the reference tree):
 //   kernels_find.hpp    k_find2 / k_find      GCSA::find                 include/gcsa/gcsa.h:96-110
@@ -23,8 +24,6 @@
 #include <hipcub/hipcub.hpp>
 #include <chrono>
 #include <condition_variable>
-#include <cstdio>
-
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -160,16 +159,6 @@ int fail(int code, const std::string& msg) { g_error = msg; return code; }
               std::string(#expr) + ": " + hipGetErrorString(e_)); } } while(0)
 
 inline unsigned grid_for(u64 n) { return unsigned((n + TPB - 1) / TPB); }
-
-// Host worker threads of one call.  If starting one of them throws (std::system_error: thread limit), the ones already
-// running are joined before the exception travels on -- destroying a joinable std::thread ends the process.
-struct Workers
-{
-  std::vector<std::thread> threads;
-  template<class... Args> void emplace_back(Args&&... args) { threads.emplace_back(std::forward<Args>(args)...); }
-  void join() { for(std::thread& t : threads) { if(t.joinable()) { t.join(); } } }
-  ~Workers() { join(); }
-};
 
 // what a memory budget (GCSA2_MEMORY_BUDGET_MB, read at create time) leaves for the next optional table
 inline u64 budget_left(const gcsa2_index* ix) { return ix->tune.budget_bytes > ix->bytes ? ix->tune.budget_bytes - ix->bytes : 0; }
@@ -399,14 +388,6 @@ struct DeviceGuard
   ~DeviceGuard() { if(prev >= 0) { (void)hipSetDevice(prev); } }
 };
 
-// RAII device buffer for the host-pointer entry points
-template<class T> struct DBuf
-{
-  T* p = nullptr;
-  hipError_t alloc(u64 count) { return hipMalloc(reinterpret_cast<void**>(&p), (count > 0 ? count : 1) * sizeof(T)); }
-  ~DBuf() { if(p) { (void)hipFree(p); } }
-};
-
 constexpr size_t PINNED_ARENA = size_t(8) << 20;       // per staging object
 constexpr size_t PINNED_MAX_COPY = size_t(2) << 20;    // larger transfers go straight from / to the caller's memory
 constexpr size_t DEVICE_ARENA_KEEP = size_t(512) << 20; // a larger arena is released with the call that needed it
@@ -603,6 +584,8 @@ struct Scratch
 };
 
 }  // namespace
+
+#include "host_batch.hpp"
 
 namespace {
 
@@ -2078,95 +2061,17 @@ inline bool offsets_ok(const uint64_t* offsets, uint64_t nq, u64* longest = null
 
 namespace {
 
-// ---- large host batches: chunked, double-buffered host -> device -> host pipeline -----------------------------------------
-// A batch of millions of patterns in pageable host memory used to go through ONE copy in, one kernel, one copy out: 10 M
-// 32-mers took 25 ms, ten times the kernel (19 GB/s end to end).  Here PIPE_LANES host threads each take every
-// PIPE_LANES-th chunk of PIPE_CHUNK_QUERIES patterns: copy the chunk into pinned memory (rebasing its offsets), enqueue
-// H2D + k_find2 + D2H on the lane's own stream, and while that runs prepare the next chunk in the lane's other staging set;
-// a set's results are copied to the caller's array when its event has fired.  Both PCIe directions, the kernel and the host
-// copies overlap; what bounds the batch is the host's memcpy rate (56 bytes per 32-mer query through pinned memory).
-// (lanes: tune.pipe_lanes, GCSA2_PIPE_LANES, 1..16, default 6; patterns per chunk: tune.pipe_chunk, GCSA2_PIPE_CHUNK = log2, default 18.
-// Round 4 re-measured the shape on the headline index, one live image re-shaped with gcsa2_index_set_pipeline: 12 lanes x 2^17
-// -- round 3's choice -- 1.4-1.8 G packed 32-mers/s, 6 lanes x 2^18 2.1-2.5 G; 0.9-1.0 -> 1.15-1.3 G for the bytes interface.  The
-// boxes give a container 16 CPUs' worth of time: twelve spinning lanes plus the runtime's own threads run into that quota --
-// with hipEventBlockingSync twelve lanes gain 20 %, six gain nothing; profiles/r04_host.md.)
-constexpr u64 PIPE_CHUNK_BYTES = u64(8) << 20;     // per chunk: at most this many pattern bytes, and tune.pipe_chunk patterns (GCSA2_PIPE_CHUNK = log2, 15..20, default 18)
-constexpr u64 PIPE_MIN_QUERIES = u64(1) << 19;                                       // smaller batches take the single-copy path
-constexpr int PIPE_PATTERN_TOO_LONG = 1;                                             // internal: not a gcsa2_status
+// ---- large host batches: the two chunk sources of the host pipeline (host_batch.hpp: pipe_run) -----------------------------
 
-inline u64 pipe_set_bytes(u64 PIPE_CHUNK_QUERIES) { return (PIPE_CHUNK_BYTES + 64) + (PIPE_CHUNK_QUERIES + 8) * 8 + PIPE_CHUNK_QUERIES * 16; }      // patterns (+ 32 bytes of phase, + slack) | offsets | ranges
-
-int pipe_prepare(const gcsa2_index* ix)
-{
-  if(!ix->pipe.empty()) { return GCSA2_OK; }
-  const unsigned PIPE_LANES = ix->tune.pipe_lanes;
-  std::vector<gcsa2_index::PipeLane> lanes(PIPE_LANES);
-  hipError_t e = hipSuccess;
-  for(gcsa2_index::PipeLane& lane : lanes)
-  {
-    if(e == hipSuccess) { e = hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking); }
-    for(gcsa2_index::PipeSet& set : lane.set)
-    {
-      if(e == hipSuccess) { e = hipHostMalloc(reinterpret_cast<void**>(&set.h), pipe_set_bytes(ix->tune.pipe_chunk), hipHostMallocDefault); }
-      if(e == hipSuccess) { e = hipMalloc(reinterpret_cast<void**>(&set.d), pipe_set_bytes(ix->tune.pipe_chunk)); }
-      if(e == hipSuccess) { e = hipEventCreateWithFlags(&set.done, hipEventDisableTiming | (ix->tune.pipe_blocking ? hipEventBlockingSync : 0)); }
-    }
-  }
-  if(e != hipSuccess)
-  {
-    for(gcsa2_index::PipeLane& lane : lanes)
-    {
-      for(gcsa2_index::PipeSet& set : lane.set)
-      {
-        if(set.h) { (void)hipHostFree(set.h); } if(set.d) { (void)hipFree(set.d); } if(set.done) { (void)hipEventDestroy(set.done); }
-      }
-      if(lane.stream) { (void)hipStreamDestroy(lane.stream); }
-    }
-    return fail(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("host pipeline: ") + hipGetErrorString(e));
-  }
-  ix->pipe = std::move(lanes);
-  return GCSA2_OK;
-}
-
-// The ranges of a chunk travel home as (sp, length) pairs in the narrowest exact form (comm.hpp: k_pack_ranges32 / 40): 8 bytes
-// per query below 2^32 path nodes and edges, 10 below 2^40, else the 16 bytes of the u64 pairs.  A lane widens them into the
-// caller's array when it retires the chunk.
-inline u64 pipe_wire_bytes(const gcsa2_index* ix)
-{
-  const u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
-  return (top < (u64(1) << 32) ? 8 : (top < (u64(1) << 40) ? 10 : 16));
-}
-
-inline void pipe_widen(const char* h, u64 count, u64 wire, u64* dst)
-{
-  if(wire == 10)                     // (sp, length) as five u16
-  {
-    const unsigned short* w = reinterpret_cast<const unsigned short*>(h);
-    for(u64 i = 0; i < count; i++, w += 5)
-    {
-      const u64 sp = u64(w[0]) | (u64(w[1]) << 16) | (u64(w[4] & 0xFF) << 32), len = u64(w[2]) | (u64(w[3]) << 16) | (u64(w[4] >> 8) << 32);
-      dst[2 * i] = sp; dst[2 * i + 1] = sp + len - 1;
-    }
-  }
-  else                               // (sp, length) as u32 pairs
-  {
-    const u32* w = reinterpret_cast<const u32*>(h);
-    for(u64 i = 0; i < count; i++) { dst[2 * i] = w[2 * i]; dst[2 * i + 1] = u64(w[2 * i]) + u64(w[2 * i + 1]) - 1; }
-  }
-}
-
+// Patterns as bytes with offsets: chunks of at most PIPE_CHUNK_QUERIES patterns and PIPE_CHUNK_BYTES pattern bytes.
 int find_pipelined(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t* ranges)
 {
   std::lock_guard<std::mutex> hold(ix->pipe_lock);
-  // patterns per chunk: the handle's setting, less for a batch too small to give every lane two chunks of that size
-  u64 PIPE_CHUNK_QUERIES = ix->tune.pipe_chunk;
-  { const u64 even = ((nq / (2 * u64(ix->tune.pipe_lanes)) + 63) & ~u64(63)), least = u64(1) << 15;
-    if(even < PIPE_CHUNK_QUERIES) { PIPE_CHUNK_QUERIES = (even > least ? even : least); } }
-  int rc = pipe_prepare(ix);
+  u64 PIPE_CHUNK_QUERIES = 0;
+  int rc = pipe_begin(ix, nq, PIPE_CHUNK_QUERIES);
   if(rc != GCSA2_OK) { return rc; }
-  // chunk boundaries: at most PIPE_CHUNK_QUERIES patterns and PIPE_CHUNK_BYTES pattern bytes each.  The offsets are validated
-  // by the lanes, chunk by chunk, while they rebase them (a serial pass over 10 M offsets costs as much as the whole batch);
-  // here only the boundaries are looked at, defensively.
+  // chunk boundaries.  The offsets are validated by the lanes, chunk by chunk, while they rebase them (a serial pass over
+  // 10 M offsets costs as much as the whole batch); here only the boundaries are looked at, defensively.
   std::vector<u64> cut(1, 0);
   while(cut.back() < nq)
   {
@@ -2182,204 +2087,85 @@ int find_pipelined(const gcsa2_index* ix, const uint8_t* patterns, const uint64_
     }
     cut.push_back(e);
   }
-  const u64 chunks = cut.size() - 1;
-  // A caller's buffer that is already page-locked (hipHostMalloc / hipHostRegister: a pinned torch tensor, the facade's own
-  // arena) is handed to the copy engines where it lies; only pageable memory goes through the lanes' pinned staging sets.
-  auto page_locked = [](const void* first, u64 bytes) -> bool
-  {
-    if(bytes == 0) { return false; }
-    hipPointerAttribute_t a, b;
-    const bool yes = hipPointerGetAttributes(&a, first) == hipSuccess && a.type == hipMemoryTypeHost &&
-                     hipPointerGetAttributes(&b, static_cast<const char*>(first) + bytes - 1) == hipSuccess && b.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return yes;
-  };
+  // each of the caller's three arrays on its own: where it lies when it is page-locked, through the lane's pinned set when not
   const bool direct_pat = page_locked(patterns, offsets[nq] - offsets[0]), direct_off = page_locked(offsets, (nq + 1) * sizeof(u64)),
              direct_out = page_locked(ranges, 2 * nq * sizeof(u64));
-  const unsigned PIPE_LANES = ix->tune.pipe_lanes;
-  // pageable result arrays are filled by the lanes anyway: their ranges come home in the narrow form (the pattern bytes of the
-  // chunk have been consumed by then: their place in both staging buffers takes it); a page-locked array is written in place
+  // pageable result arrays are filled by the lanes anyway: their ranges come home in the narrow form; a page-locked array is
+  // written in place, which takes the 16-byte pairs.  (The packed form below keeps the narrow wire even then; the two
+  // choices have not been measured against each other.)
   const u64 wire = (direct_out ? 16 : pipe_wire_bytes(ix));
-  std::vector<int> status(PIPE_LANES, GCSA2_OK);
-  std::vector<std::string> messages(PIPE_LANES);
-  auto work = [&](unsigned t)
+  auto stage = [&](u64 c, gcsa2_index::PipeLane& lane, gcsa2_index::PipeSet& set, Outcome& out) -> bool
   {
-    DeviceGuard guard(ix->device);
-    gcsa2_index::PipeLane& lane = ix->pipe[t];
-    auto fail_lane = [&](const char* what, hipError_t e) { status[t] = GCSA2_ERR_HIP; messages[t] = std::string(what) + ": " + hipGetErrorString(e); };
-    auto retire = [&](gcsa2_index::PipeSet& set) -> bool        // wait for the set's chunk and hand its ranges to the caller
+    const u64 b = cut[c], e = cut[c + 1], count = e - b, base = offsets[b], bytes = offsets[e] - base;
+    char* h_pat = set.h; u64* h_off = reinterpret_cast<u64*>(set.h + (PIPE_CHUNK_BYTES + 64));
+    // the chunk's pattern bytes land at the same phase within 16 bytes as in the caller's array (the kernel reads aligned
+    // words around a pattern's ends); with the caller's absolute offsets the kernel gets the pointer moved back by `base`
+    const u64 phase = 16 + (base & 15);
+    // patterns of one length (k-mer batches): the chunk's offsets are base + i * length, made on the device instead of sent
+    const u64 stride = (offsets[b + 1] - base);
+    u64 bad = 0, ragged = 0;
+    if(direct_off) { for(u64 i = 1; i <= count; i++) { const u64 o = offsets[b + i]; bad |= u64(o < offsets[b + i - 1]); ragged |= (o - base) ^ (i * stride); } }
+    else { for(u64 i = 0; i <= count; i++) { const u64 o = offsets[b + i]; h_off[i] = o - base; bad |= u64(i > 0 && o < offsets[b + i - 1]); ragged |= (o - base) ^ (i * stride); } }
+    if(bad != 0 || bytes > PIPE_CHUNK_BYTES) { out.set(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets are not non-decreasing"); return false; }
+    const bool uniform = (ragged == 0);
+    char* d_pat = set.d; u64* d_off = reinterpret_cast<u64*>(set.d + (PIPE_CHUNK_BYTES + 64));
+    hipError_t err = hipSuccess;
+    if(direct_pat) { err = hipMemcpyAsync(d_pat + phase, patterns + base, bytes, hipMemcpyHostToDevice, lane.stream); }
+    else
     {
-      if(!set.busy) { return true; }
-      hipError_t e = hipEventSynchronize(set.done);
-      if(e != hipSuccess) { fail_lane("hipEventSynchronize", e); return false; }
-      if(wire != 16) { pipe_widen(set.h, set.count, wire, ranges + 2 * set.first); }
-      else if(!direct_out)
-      {
-        const char* h_out = set.h + (PIPE_CHUNK_BYTES + 64) + (PIPE_CHUNK_QUERIES + 8) * 8;
-        std::memcpy(ranges + 2 * set.first, h_out, set.count * 16);
-      }
-      set.busy = false;
-      return true;
-    };
-    unsigned turn = 0;
-    for(u64 c = t; c < chunks && status[t] == GCSA2_OK; c += PIPE_LANES, turn ^= 1)
-    {
-      gcsa2_index::PipeSet& set = lane.set[turn];
-      if(!retire(set)) { break; }
-      const u64 b = cut[c], e = cut[c + 1], count = e - b, base = offsets[b], bytes = offsets[e] - base;
-      char* h_pat = set.h; u64* h_off = reinterpret_cast<u64*>(set.h + (PIPE_CHUNK_BYTES + 64));
-      char* h_out = reinterpret_cast<char*>(h_off + PIPE_CHUNK_QUERIES + 8);
-      // the chunk's pattern bytes land at the same phase within 16 bytes as in the caller's array (the kernel reads aligned
-      // words around a pattern's ends); with the caller's absolute offsets the kernel gets the pointer moved back by `base`
-      const u64 phase = 16 + (base & 15);
-      // patterns of one length (k-mer batches): the chunk's offsets are base + i * length, made on the device instead of sent
-      const u64 stride = (offsets[b + 1] - base);
-      u64 bad = 0, ragged = 0;
-      if(direct_off) { for(u64 i = 1; i <= count; i++) { const u64 o = offsets[b + i]; bad |= u64(o < offsets[b + i - 1]); ragged |= (o - base) ^ (i * stride); } }
-      else { for(u64 i = 0; i <= count; i++) { const u64 o = offsets[b + i]; h_off[i] = o - base; bad |= u64(i > 0 && o < offsets[b + i - 1]); ragged |= (o - base) ^ (i * stride); } }
-      if(bad != 0 || bytes > PIPE_CHUNK_BYTES) { status[t] = GCSA2_ERR_INVALID_ARGUMENT; messages[t] = "pattern offsets are not non-decreasing"; break; }
-      const bool uniform = (ragged == 0);
-      char* d_pat = set.d; u64* d_off = reinterpret_cast<u64*>(set.d + (PIPE_CHUNK_BYTES + 64));
-      u64* d_out = d_off + PIPE_CHUNK_QUERIES + 8;
-      hipError_t err = hipSuccess;
-      if(direct_pat) { err = hipMemcpyAsync(d_pat + phase, patterns + base, bytes, hipMemcpyHostToDevice, lane.stream); }
-      else
-      {
-        std::memcpy(h_pat + phase, patterns + base, bytes);
-        err = hipMemcpyAsync(d_pat, h_pat, (phase + bytes + 7) / 8 * 8, hipMemcpyHostToDevice, lane.stream);
-      }
-      if(err == hipSuccess && uniform)
-      {
-        hipLaunchKernelGGL(k_uniform_offsets, dim3(grid_for(count + 1)), dim3(TPB), 0, lane.stream, d_off, count + 1, stride);
-        err = hipGetLastError();
-      }
-      else if(err == hipSuccess)
-      {
-        err = hipMemcpyAsync(d_off, direct_off ? offsets + b : h_off, (count + 1) * sizeof(u64), hipMemcpyHostToDevice, lane.stream);
-      }
-      if(err != hipSuccess) { fail_lane("hipMemcpyAsync", err); break; }
-      const uint8_t* d_first = reinterpret_cast<const uint8_t*>(d_pat + phase) - (direct_off && !uniform ? base : 0);
-      int rc_find = gcsa2_find_device(ix, d_first, d_off, count, d_out, lane.stream);
-      if(rc_find != GCSA2_OK) { status[t] = rc_find; messages[t] = g_error; break; }
-      if(wire != 16)
-      {
-        const int rc_pack = (wire == 10 ? gcsa2_pack_ranges40_device(d_out, count, set.d, lane.stream) : gcsa2_pack_ranges32_device(d_out, count, reinterpret_cast<uint32_t*>(set.d), lane.stream));
-        if(rc_pack != GCSA2_OK) { status[t] = rc_pack; messages[t] = g_error; break; }
-        err = hipMemcpyAsync(set.h, set.d, count * wire, hipMemcpyDeviceToHost, lane.stream);
-      }
-      else { err = hipMemcpyAsync(direct_out ? reinterpret_cast<char*>(ranges + 2 * b) : h_out, d_out, count * 16, hipMemcpyDeviceToHost, lane.stream); }
-      if(err == hipSuccess) { err = hipEventRecord(set.done, lane.stream); }
-      if(err != hipSuccess) { fail_lane("hipMemcpyAsync / hipEventRecord", err); break; }
-      set.busy = true; set.first = b; set.count = count;
+      std::memcpy(h_pat + phase, patterns + base, bytes);
+      err = hipMemcpyAsync(d_pat, h_pat, (phase + bytes + 7) / 8 * 8, hipMemcpyHostToDevice, lane.stream);
     }
-    for(gcsa2_index::PipeSet& set : lane.set) { if(status[t] == GCSA2_OK) { (void)retire(set); } }
-    if(status[t] != GCSA2_OK)           // nothing of this call may still be in flight when it returns
+    if(err == hipSuccess && uniform)
     {
-      (void)hipStreamSynchronize(lane.stream);
-      for(gcsa2_index::PipeSet& set : lane.set) { set.busy = false; }
+      hipLaunchKernelGGL(k_uniform_offsets, dim3(grid_for(count + 1)), dim3(TPB), 0, lane.stream, d_off, count + 1, stride);
+      err = hipGetLastError();
     }
+    else if(err == hipSuccess)
+    {
+      err = hipMemcpyAsync(d_off, direct_off ? offsets + b : h_off, (count + 1) * sizeof(u64), hipMemcpyHostToDevice, lane.stream);
+    }
+    if(err != hipSuccess) { out.hip_error("hipMemcpyAsync", err); return false; }
+    const uint8_t* d_first = reinterpret_cast<const uint8_t*>(d_pat + phase) - (direct_off && !uniform ? base : 0);
+    const int rc_find = gcsa2_find_device(ix, d_first, d_off, count, reinterpret_cast<u64*>(set.d + pipe_out_at(PIPE_CHUNK_QUERIES)), lane.stream);
+    if(rc_find != GCSA2_OK) { out.set(rc_find, g_error); return false; }
+    set.first = b; set.count = count;
+    return true;
   };
-  Workers workers;
-  const unsigned lanes = unsigned(chunks < PIPE_LANES ? chunks : PIPE_LANES);
-  for(unsigned t = 1; t < lanes; t++) { workers.emplace_back(work, t); }
-  work(0);
-  workers.join();
-  for(unsigned t = 0; t < lanes; t++) { if(status[t] != GCSA2_OK) { return fail(status[t], "pipeline lane " + std::to_string(t) + ": " + messages[t]); } }
-  return GCSA2_OK;
+  return pipe_run(ix, cut.size() - 1, PIPE_CHUNK_QUERIES, wire, direct_out, ranges, stage);
 }
 
-// The same pipeline for patterns that arrive as 2-bit codes of one length (gcsa2_find_batch_packed): a chunk is its code words
-// up the link (8 bytes per 32 characters), one launch, its ranges down; no offsets at all.
+// Patterns as 2-bit codes of one length (gcsa2_find_batch_packed): a chunk is a fixed number of patterns, its code words up
+// the link (8 bytes per 32 characters), one launch, its ranges down; no offsets at all.
 int find_packed_pipelined(const gcsa2_index* ix, const uint64_t* codes, u64 length, uint64_t nq, uint64_t* ranges)
 {
   std::lock_guard<std::mutex> hold(ix->pipe_lock);
-  // patterns per chunk: the handle's setting, less for a batch too small to give every lane two chunks of that size
-  u64 PIPE_CHUNK_QUERIES = ix->tune.pipe_chunk;
-  { const u64 even = ((nq / (2 * u64(ix->tune.pipe_lanes)) + 63) & ~u64(63)), least = u64(1) << 15;
-    if(even < PIPE_CHUNK_QUERIES) { PIPE_CHUNK_QUERIES = (even > least ? even : least); } }
-  int rc = pipe_prepare(ix);
+  u64 PIPE_CHUNK_QUERIES = 0;
+  int rc = pipe_begin(ix, nq, PIPE_CHUNK_QUERIES);
   if(rc != GCSA2_OK) { return rc; }
   const u64 words = (length + 31) >> 5;
   u64 per_chunk = PIPE_CHUNK_BYTES / (8 * words);
   if(per_chunk > PIPE_CHUNK_QUERIES) { per_chunk = PIPE_CHUNK_QUERIES; }
   if(per_chunk == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "packed patterns: one pattern exceeds a pipeline chunk"); }
-  const u64 chunks = (nq + per_chunk - 1) / per_chunk;
-  auto page_locked = [](const void* first, u64 bytes) -> bool
-  {
-    if(bytes == 0) { return false; }
-    hipPointerAttribute_t a, b;
-    const bool yes = hipPointerGetAttributes(&a, first) == hipSuccess && a.type == hipMemoryTypeHost &&
-                     hipPointerGetAttributes(&b, static_cast<const char*>(first) + bytes - 1) == hipSuccess && b.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return yes;
-  };
+  // the narrow wire whenever the index allows it; a page-locked result array is written in place only on the 16-byte wire
   const bool direct_in = page_locked(codes, nq * words * 8), direct_out = page_locked(ranges, 2 * nq * sizeof(u64));
-  const unsigned PIPE_LANES = ix->tune.pipe_lanes;
-  std::vector<int> status(PIPE_LANES, GCSA2_OK);
-  std::vector<std::string> messages(PIPE_LANES);
-  const u64 out_at = (PIPE_CHUNK_BYTES + 64) + (PIPE_CHUNK_QUERIES + 8) * 8;      // where a set keeps its ranges (pipe_set_bytes)
-  // the ranges travel home as (sp, length) pairs in the narrowest exact form (comm.hpp): 8 bytes below 2^32 path nodes and
-  // edges, 10 below 2^40, else the 16 bytes of the u64 pairs
-  const u64 wire = pipe_wire_bytes(ix);
-  auto work = [&](unsigned t)
+  auto stage = [&](u64 c, gcsa2_index::PipeLane& lane, gcsa2_index::PipeSet& set, Outcome& out) -> bool
   {
-    DeviceGuard guard(ix->device);
-    gcsa2_index::PipeLane& lane = ix->pipe[t];
-    auto fail_lane = [&](const char* what, hipError_t e) { status[t] = GCSA2_ERR_HIP; messages[t] = std::string(what) + ": " + hipGetErrorString(e); };
-    auto retire = [&](gcsa2_index::PipeSet& set) -> bool
+    const u64 b = c * per_chunk, count = (nq - b < per_chunk ? nq - b : per_chunk), bytes = count * words * 8;
+    hipError_t err = hipSuccess;
+    if(direct_in) { err = hipMemcpyAsync(set.d, codes + b * words, bytes, hipMemcpyHostToDevice, lane.stream); }
+    else
     {
-      if(!set.busy) { return true; }
-      hipError_t e = hipEventSynchronize(set.done);
-      if(e != hipSuccess) { fail_lane("hipEventSynchronize", e); return false; }
-      u64* dst = ranges + 2 * set.first;
-      if(wire != 16) { pipe_widen(set.h, set.count, wire, dst); }
-      else if(!direct_out) { std::memcpy(dst, set.h + out_at, set.count * 16); }
-      set.busy = false;
-      return true;
-    };
-    unsigned turn = 0;
-    for(u64 c = t; c < chunks && status[t] == GCSA2_OK; c += PIPE_LANES, turn ^= 1)
-    {
-      gcsa2_index::PipeSet& set = lane.set[turn];
-      if(!retire(set)) { break; }
-      const u64 b = c * per_chunk, count = (nq - b < per_chunk ? nq - b : per_chunk), bytes = count * words * 8;
-      hipError_t err = hipSuccess;
-      if(direct_in) { err = hipMemcpyAsync(set.d, codes + b * words, bytes, hipMemcpyHostToDevice, lane.stream); }
-      else
-      {
-        std::memcpy(set.h, codes + b * words, bytes);
-        err = hipMemcpyAsync(set.d, set.h, bytes, hipMemcpyHostToDevice, lane.stream);
-      }
-      if(err != hipSuccess) { fail_lane("hipMemcpyAsync", err); break; }
-      u64* d_out = reinterpret_cast<u64*>(set.d + out_at);
-      int rc_find = gcsa2_find_packed_device(ix, reinterpret_cast<const u64*>(set.d), length, count, d_out, lane.stream);
-      if(rc_find != GCSA2_OK) { status[t] = rc_find; messages[t] = g_error; break; }
-      if(wire == 16) { err = hipMemcpyAsync(direct_out ? reinterpret_cast<char*>(ranges + 2 * b) : set.h + out_at, d_out, count * 16, hipMemcpyDeviceToHost, lane.stream); }
-      else
-      {
-        // the code words have been consumed: their place takes the narrow form of the ranges, which is what travels
-        int rc_pack = (wire == 10 ? gcsa2_pack_ranges40_device(d_out, count, set.d, lane.stream) : gcsa2_pack_ranges32_device(d_out, count, reinterpret_cast<uint32_t*>(set.d), lane.stream));
-        if(rc_pack != GCSA2_OK) { status[t] = rc_pack; messages[t] = g_error; break; }
-        err = hipMemcpyAsync(set.h, set.d, count * wire, hipMemcpyDeviceToHost, lane.stream);
-      }
-      if(err == hipSuccess) { err = hipEventRecord(set.done, lane.stream); }
-      if(err != hipSuccess) { fail_lane("hipMemcpyAsync / hipEventRecord", err); break; }
-      set.busy = true; set.first = b; set.count = count;
+      std::memcpy(set.h, codes + b * words, bytes);
+      err = hipMemcpyAsync(set.d, set.h, bytes, hipMemcpyHostToDevice, lane.stream);
     }
-    for(gcsa2_index::PipeSet& set : lane.set) { if(status[t] == GCSA2_OK) { (void)retire(set); } }
-    if(status[t] != GCSA2_OK)
-    {
-      (void)hipStreamSynchronize(lane.stream);
-      for(gcsa2_index::PipeSet& set : lane.set) { set.busy = false; }
-    }
+    if(err != hipSuccess) { out.hip_error("hipMemcpyAsync", err); return false; }
+    const int rc_find = gcsa2_find_packed_device(ix, reinterpret_cast<const u64*>(set.d), length, count, reinterpret_cast<u64*>(set.d + pipe_out_at(PIPE_CHUNK_QUERIES)), lane.stream);
+    if(rc_find != GCSA2_OK) { out.set(rc_find, g_error); return false; }
+    set.first = b; set.count = count;
+    return true;
   };
-  Workers workers;
-  const unsigned lanes = unsigned(chunks < PIPE_LANES ? chunks : PIPE_LANES);
-  for(unsigned t = 1; t < lanes; t++) { workers.emplace_back(work, t); }
-  work(0);
-  workers.join();
-  for(unsigned t = 0; t < lanes; t++) { if(status[t] != GCSA2_OK) { return fail(status[t], "pipeline lane " + std::to_string(t) + ": " + messages[t]); } }
-  return GCSA2_OK;
+  return pipe_run(ix, (nq + per_chunk - 1) / per_chunk, PIPE_CHUNK_QUERIES, pipe_wire_bytes(ix), direct_out, ranges, stage);
 }
 
 }  // namespace
@@ -3015,10 +2801,6 @@ namespace {
 int match_stats_launch(const gcsa2_index* ix, int variant, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, u64 total_bytes,
                        uint16_t* d_ms, uint64_t* d_ranges, uint64_t* d_fallbacks, hipStream_t st, const BreakSink* sink = nullptr);
 int group_comm_init(gcsa2_group* g);
-int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
-                        uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks);
-// (large host batches of matching statistics / break points go in pieces of tune.ms_piece_bytes -- GCSA2_MS_PIECE_MB, 32 MB -- from two pieces' worth on)
-
 }  // namespace
 
 #include "comm.hpp"
@@ -3562,9 +3344,8 @@ int gcsa2_group_find_batch(const gcsa2_group* g, const uint8_t* patterns, const 
     {
       try
       {
-        std::vector<u64> local(count + 1);
-        for(u64 i = 0; i <= count; i++) { local[i] = offsets[b + i] - offsets[b]; }
-        status[r] = gcsa2_find_batch(g->replicas[r], patterns + offsets[b], local.data(), count, ranges + 2 * b);
+        std::vector<u64> local;
+        status[r] = gcsa2_find_batch(g->replicas[r], patterns + offsets[b], rebase_piece(offsets, b, count, local), count, ranges + 2 * b);
         if(status[r] != GCSA2_OK) { messages[r] = g_error; }     // g_error is thread-local
       }
       catch(const std::exception& e) { status[r] = GCSA2_ERR_OUT_OF_MEMORY; messages[r] = e.what(); }
@@ -3867,6 +3648,88 @@ int gcsa2_match_breaks_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
   return GCSA2_OK;
 }
 
+namespace {
+
+// The break points of a large host batch, in pieces like the dense statistics of match_stats_pieced (a MEM finder's reads live in host memory:
+// one copy in, one kernel, copies out leaves the device idle two thirds of the time).  A piece's records land in the caller's
+// array behind those of the pieces before it, so the pieces COMMIT in order: when its kernel has finished a piece knows its
+// number of records, waits for the running total of the pieces before it (they started earlier; the wait is the tail of one
+// kernel at most), takes its place and downloads there.  The device-side record buffer of a piece is sized by an estimate
+// (one record per 8 pattern bytes; a piece that needs more runs again with the exact size).  Once the caller's capacity is
+// exceeded the remaining pieces only count: GCSA2_ERR_BUFFER_TOO_SMALL with the number of records of the whole batch.
+int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                        uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks)
+{
+  const std::vector<u64> cut = cut_pieces(offsets, nq, ix->tune.ms_piece_bytes);
+  const u64 pieces = cut.size() - 1;
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  struct Order { std::mutex m; std::condition_variable cv; u64 next = 0, base = 0; bool failed = false; } order;
+  auto work = [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard guard(ix->device);
+    std::vector<u64> local;
+    auto give_up = [&](int rc, const std::string& what)
+    {
+      out.set(rc, what);
+      std::lock_guard<std::mutex> hold(order.m);
+      order.failed = true;
+      order.cv.notify_all();
+    };
+    try {
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      u64 room = bytes / 8 + count + 1, found = 0;
+      bool placed = false;
+      for(int attempt = 0; attempt < 2 && !placed && out.status == GCSA2_OK; attempt++)
+      {
+        Lease lease(ix);
+        hipError_t e = lease.begin(Lease::need(bytes + 16) + 2 * Lease::need((count + 1) * 8) + Lease::need(room * 32) + Lease::need(2 * count * 8) + Lease::need(count * 8));
+        if(e != hipSuccess) { give_up(GCSA2_ERR_OUT_OF_MEMORY, std::string("staging of a piece: ") + hipGetErrorString(e)); break; }
+        u8* d_pat = lease.dev<u8>(bytes + 16); u64* d_off = lease.dev<u64>(count + 1); u64* d_boff = lease.dev<u64>(count + 1);
+        gcsa2_break* d_brk = reinterpret_cast<gcsa2_break*>(lease.dev<u64>(4 * room));
+        u64* d_rng = lease.dev<u64>(2 * count); u64* d_fb = lease.dev<u64>(count);
+        e = lease.up(d_pat, patterns + first, bytes);
+        if(e == hipSuccess) { e = lease.up(d_off, local.data(), (count + 1) * sizeof(u64)); }
+        if(e != hipSuccess) { give_up(GCSA2_ERR_HIP, std::string("upload of a piece: ") + hipGetErrorString(e)); break; }
+        const int rc = gcsa2_match_breaks_device(ix, d_pat, d_off, count, bytes, 0, min_length, d_boff, d_brk, room, &found, d_rng, d_fb, lease.stream());
+        if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && found > room) { room = found; (void)lease.finish(); continue; }    // the estimate was short: once more, exactly
+        if(rc != GCSA2_OK) { give_up(rc, g_error); break; }
+        // commit in piece order: the position of this piece's first record
+        u64 at = 0;
+        {
+          std::unique_lock<std::mutex> hold(order.m);
+          order.cv.wait(hold, [&]() { return order.next == c || order.failed; });
+          if(order.failed) { out.set(GCSA2_ERR_HIP, "another piece of the batch failed"); out.echo = true; break; }      // (reported only if no piece says why)
+          at = order.base; order.base += found; order.next = c + 1;
+          order.cv.notify_all();
+        }
+        placed = true;
+        if(at + found <= capacity)
+        {
+          e = lease.down(local.data(), d_boff, (count + 1) * sizeof(u64));
+          if(e == hipSuccess && found > 0) { e = lease.down(breaks + at, d_brk, found * sizeof(gcsa2_break)); }
+          if(e == hipSuccess && ranges != nullptr) { e = lease.down(ranges + 2 * b, d_rng, 2 * count * sizeof(u64)); }
+          if(e == hipSuccess && fallbacks != nullptr) { e = lease.down(fallbacks + b, d_fb, count * sizeof(u64)); }
+          if(e == hipSuccess) { e = lease.finish(); }
+          if(e != hipSuccess) { give_up(GCSA2_ERR_HIP, std::string("download of a piece: ") + hipGetErrorString(e)); break; }
+          for(u64 i = 0; i <= count; i++) { break_offsets[b + i] = local[i] + at; }     // (the last entry is the next piece's first: same value)
+        }
+        else { (void)lease.finish(); }
+      }
+    }
+    } catch(const std::exception& e) { give_up(GCSA2_ERR_OUT_OF_MEMORY, std::string("a piece of the batch: ") + e.what()); }     // (here, not in fan_out: the other pieces must not wait for this one)
+  };
+  const int rc = fan_out(threads, nullptr, work);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_breaks = order.base;
+  if(order.base > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "break buffer too small"); }
+  return GCSA2_OK;
+}
+
+}  // namespace
+
 // The break points of a batch in host memory: one copy in, gcsa2_match_breaks_device, the CSR out.
 int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
                              uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks,
@@ -3976,8 +3839,8 @@ int match_stats_single(const gcsa2_index* ix, const uint8_t* patterns, const uin
 // eight threads or 8 MB pieces change nothing: what is left is the rate of copies to and from pageable memory,
 // tests/perf/ms_host_batch.py.  Staging those copies ourselves through a ring of pinned 2 MB pieces was measured and is
 // twice as slow as the runtime's own path for pageable memory: 47 ms in a row, 24-28 ms in pieces.)
-// (pieces of tune.ms_piece_bytes = 32 MB (GCSA2_MS_PIECE_MB) for batches of two pieces' worth (64 MB) and more, on tune.ms_threads = 4 host threads: declared with
-// the forward declarations above.  Round 4 re-measured the piece size, 1 M x 256 bp: dense statistics on the chr22-like index 15.9-17.4 ms
+// (pieces of tune.ms_piece_bytes = 32 MB (GCSA2_MS_PIECE_MB) for batches of two pieces' worth (64 MB) and more, on tune.ms_threads = 4 host threads: fields of
+// gcsa2_index::Tuning.  Round 4 re-measured the piece size, 1 M x 256 bp: dense statistics on the chr22-like index 15.9-17.4 ms
 // with 16 MB, 15.0 with 32, 16.1 with 64, 18.9 with 128, 22.3 in one copy; break points of at least 20 bp on the 5.73 G-node index 24.5 /
 // 16.7 / 16.9 / 19.5 ms and 17.9 in one copy -- a piece must still fill the device: the kernel's time per pattern is latency, not work;
 // profiles/r04_host.md)
@@ -3985,133 +3848,20 @@ int match_stats_single(const gcsa2_index* ix, const uint8_t* patterns, const uin
 int match_stats_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, u64 longest,
                        uint16_t* ms, uint64_t* ranges, uint64_t* fallbacks)
 {
-  std::vector<u64> cut(1, 0);
-  while(cut.back() < nq)
-  {
-    const u64 b = cut.back();
-    u64 lo = b + 1, hi = nq;                               // largest e with offsets[e] - offsets[b] <= the piece size, at least one pattern
-    while(lo < hi) { const u64 mid = (lo + hi + 1) / 2; if(offsets[mid] - offsets[b] <= ix->tune.ms_piece_bytes) { lo = mid; } else { hi = mid - 1; } }
-    cut.push_back(lo);
-  }
+  const std::vector<u64> cut = cut_pieces(offsets, nq, ix->tune.ms_piece_bytes);
   const u64 pieces = cut.size() - 1;
   const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  std::vector<int> status(threads, GCSA2_OK);
-  std::vector<std::string> messages(threads);
-  auto work = [&](unsigned t)
+  return fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
   {
-    try                                   // (an exception must not leave a worker thread: std::terminate)
-    {
-      std::vector<u64> local;
-      for(u64 c = t; c < pieces && status[t] == GCSA2_OK; c += threads)
-      {
-        const u64 b = cut[c], count = cut[c + 1] - b, base = offsets[b];
-        local.resize(count + 1);
-        for(u64 i = 0; i <= count; i++) { local[i] = offsets[b + i] - base; }
-        status[t] = match_stats_single(ix, patterns + base, local.data(), count, longest, ms + base, ranges + 2 * b,
-                                       fallbacks != nullptr ? fallbacks + b : nullptr);
-        if(status[t] != GCSA2_OK) { messages[t] = g_error; }
-      }
-    }
-    catch(const std::exception& e) { status[t] = GCSA2_ERR_OUT_OF_MEMORY; messages[t] = std::string("a piece of the batch: ") + e.what(); }
-  };
-  Workers workers;
-  for(unsigned t = 1; t < threads; t++) { workers.emplace_back(work, t); }
-  work(0);
-  workers.join();
-  for(unsigned t = 0; t < threads; t++) { if(status[t] != GCSA2_OK) { return fail(status[t], messages[t]); } }
-  return GCSA2_OK;
-}
-
-// The break points of a large host batch, in pieces like the dense statistics above (a MEM finder's reads live in host memory:
-// one copy in, one kernel, copies out leaves the device idle two thirds of the time).  A piece's records land in the caller's
-// array behind those of the pieces before it, so the pieces COMMIT in order: when its kernel has finished a piece knows its
-// number of records, waits for the running total of the pieces before it (they started earlier; the wait is the tail of one
-// kernel at most), takes its place and downloads there.  The device-side record buffer of a piece is sized by an estimate
-// (one record per 8 pattern bytes; a piece that needs more runs again with the exact size).  Once the caller's capacity is
-// exceeded the remaining pieces only count: GCSA2_ERR_BUFFER_TOO_SMALL with the number of records of the whole batch.
-int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
-                        uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks)
-{
-  std::vector<u64> cut(1, 0);
-  while(cut.back() < nq)
-  {
-    const u64 b = cut.back();
-    u64 lo = b + 1, hi = nq;                               // largest e with offsets[e] - offsets[b] <= the piece size, at least one pattern
-    while(lo < hi) { const u64 mid = (lo + hi + 1) / 2; if(offsets[mid] - offsets[b] <= ix->tune.ms_piece_bytes) { lo = mid; } else { hi = mid - 1; } }
-    cut.push_back(lo);
-  }
-  const u64 pieces = cut.size() - 1;
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  std::vector<int> status(threads, GCSA2_OK);
-  std::vector<std::string> messages(threads);
-  struct Order { std::mutex m; std::condition_variable cv; u64 next = 0, base = 0; bool failed = false; } order;
-  auto work = [&](unsigned t)
-  {
-    DeviceGuard guard(ix->device);
     std::vector<u64> local;
-    auto give_up = [&](int rc, const std::string& what)
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
     {
-      status[t] = rc; messages[t] = what;
-      std::lock_guard<std::mutex> hold(order.m);
-      order.failed = true;
-      order.cv.notify_all();
-    };
-    try {
-    for(u64 c = t; c < pieces && status[t] == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      local.resize(count + 1);
-      for(u64 i = 0; i <= count; i++) { local[i] = offsets[b + i] - first; }
-      u64 room = bytes / 8 + count + 1, found = 0;
-      bool placed = false;
-      for(int attempt = 0; attempt < 2 && !placed && status[t] == GCSA2_OK; attempt++)
-      {
-        Lease lease(ix);
-        hipError_t e = lease.begin(Lease::need(bytes + 16) + 2 * Lease::need((count + 1) * 8) + Lease::need(room * 32) + Lease::need(2 * count * 8) + Lease::need(count * 8));
-        if(e != hipSuccess) { give_up(GCSA2_ERR_OUT_OF_MEMORY, std::string("staging of a piece: ") + hipGetErrorString(e)); break; }
-        u8* d_pat = lease.dev<u8>(bytes + 16); u64* d_off = lease.dev<u64>(count + 1); u64* d_boff = lease.dev<u64>(count + 1);
-        gcsa2_break* d_brk = reinterpret_cast<gcsa2_break*>(lease.dev<u64>(4 * room));
-        u64* d_rng = lease.dev<u64>(2 * count); u64* d_fb = lease.dev<u64>(count);
-        e = lease.up(d_pat, patterns + first, bytes);
-        if(e == hipSuccess) { e = lease.up(d_off, local.data(), (count + 1) * sizeof(u64)); }
-        if(e != hipSuccess) { give_up(GCSA2_ERR_HIP, std::string("upload of a piece: ") + hipGetErrorString(e)); break; }
-        const int rc = gcsa2_match_breaks_device(ix, d_pat, d_off, count, bytes, 0, min_length, d_boff, d_brk, room, &found, d_rng, d_fb, lease.stream());
-        if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && found > room) { room = found; (void)lease.finish(); continue; }    // the estimate was short: once more, exactly
-        if(rc != GCSA2_OK) { give_up(rc, g_error); break; }
-        // commit in piece order: the position of this piece's first record
-        u64 at = 0;
-        {
-          std::unique_lock<std::mutex> hold(order.m);
-          order.cv.wait(hold, [&]() { return order.next == c || order.failed; });
-          if(order.failed) { status[t] = GCSA2_ERR_HIP; messages[t] = "another piece of the batch failed"; break; }
-          at = order.base; order.base += found; order.next = c + 1;
-          order.cv.notify_all();
-        }
-        placed = true;
-        if(at + found <= capacity)
-        {
-          e = lease.down(local.data(), d_boff, (count + 1) * sizeof(u64));
-          if(e == hipSuccess && found > 0) { e = lease.down(breaks + at, d_brk, found * sizeof(gcsa2_break)); }
-          if(e == hipSuccess && ranges != nullptr) { e = lease.down(ranges + 2 * b, d_rng, 2 * count * sizeof(u64)); }
-          if(e == hipSuccess && fallbacks != nullptr) { e = lease.down(fallbacks + b, d_fb, count * sizeof(u64)); }
-          if(e == hipSuccess) { e = lease.finish(); }
-          if(e != hipSuccess) { give_up(GCSA2_ERR_HIP, std::string("download of a piece: ") + hipGetErrorString(e)); break; }
-          for(u64 i = 0; i <= count; i++) { break_offsets[b + i] = local[i] + at; }     // (the last entry is the next piece's first: same value)
-        }
-        else { (void)lease.finish(); }
-      }
+      const u64 b = cut[c], count = cut[c + 1] - b, base = offsets[b];
+      const int rc = match_stats_single(ix, patterns + base, rebase_piece(offsets, b, count, local), count, longest, ms + base, ranges + 2 * b,
+                                        fallbacks != nullptr ? fallbacks + b : nullptr);
+      if(rc != GCSA2_OK) { out.set(rc, g_error); }
     }
-    } catch(const std::exception& e) { give_up(GCSA2_ERR_OUT_OF_MEMORY, std::string("a piece of the batch: ") + e.what()); }     // (not out of a worker thread)
-  };
-  Workers workers;
-  for(unsigned t = 1; t < threads; t++) { workers.emplace_back(work, t); }
-  work(0);
-  workers.join();
-  for(unsigned t = 0; t < threads; t++) { if(status[t] != GCSA2_OK && messages[t] != "another piece of the batch failed") { return fail(status[t], messages[t]); } }
-  for(unsigned t = 0; t < threads; t++) { if(status[t] != GCSA2_OK) { return fail(status[t], messages[t]); } }
-  *total_breaks = order.base;
-  if(order.base > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "break buffer too small"); }
-  return GCSA2_OK;
+  });
 }
 
 }  // namespace
@@ -4961,48 +4711,32 @@ int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const u
   try {   // no C++ exception may cross the C boundary
   DeviceGuard guard(ix->device);
   g_error.clear();
-  std::vector<u64> cut(1, 0);
-  while(cut.back() < nq)
-  {
-    const u64 b = cut.back();
-    if(offsets[nq] < 2 * ix->tune.ms_piece_bytes) { cut.push_back(nq); break; }
-    u64 lo = b + 1, hi = nq;                               // largest e with offsets[e] - offsets[b] <= the piece size, at least one pattern
-    while(lo < hi) { const u64 mid = (lo + hi + 1) / 2; if(offsets[mid] - offsets[b] <= ix->tune.ms_piece_bytes) { lo = mid; } else { hi = mid - 1; } }
-    cut.push_back(lo);
-  }
+  const std::vector<u64> cut = (offsets[nq] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, nq} : cut_pieces(offsets, nq, ix->tune.ms_piece_bytes));
   const u64 pieces = cut.size() - 1;
-  struct Dev
-  {
-    void* p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void release() { for(void*& x : p) { if(x) { (void)hipFree(x); x = nullptr; } } }
-    ~Dev() { release(); }
-  } dev;
+  DBuf<u8> d_pat; DBuf<u64> d_off, d_mem_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_mems;
   u64 mbase = 0, hbase = 0;
   bool exceeded = false;
   std::vector<u64> local;
   for(u64 c = 0; c < pieces; c++)
   {
     const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-    local.resize(count + 1);
-    for(u64 i = 0; i <= count; i++) { local[i] = offsets[b + i] - first; }
+    rebase_piece(offsets, b, count, local);
     const u64 mem_room = exceeded ? 0 : mem_capacity - mbase, hit_room = exceeded ? 0 : hit_capacity - hbase;
     u64 rm = std::min(mem_room, pieces == 1 ? bytes + count : bytes / 8 + count + 1);
     u64 rh = (pieces == 1 ? hit_room : std::min(hit_room, 16 * rm));
     u64 m = 0, h = 0;
     for(int attempt = 0; attempt < 2; attempt++)
     {
-      dev.release();
-      HIP_TRY(hipMalloc(&dev.p[0], bytes + 16));
-      HIP_TRY(hipMalloc(&dev.p[1], (count + 1) * sizeof(u64)));
-      HIP_TRY(hipMalloc(&dev.p[2], (count + 1) * sizeof(u64)));
-      HIP_TRY(hipMalloc(&dev.p[3], std::max<u64>(rm, 1) * sizeof(gcsa2_mem)));
-      HIP_TRY(hipMalloc(&dev.p[4], (rm + 1) * sizeof(u64)));
-      HIP_TRY(hipMalloc(&dev.p[5], std::max<u64>(rh, 1) * sizeof(u64)));
-      if(bytes > 0) { HIP_TRY(hipMemcpy(dev.p[0], patterns + first, bytes, hipMemcpyHostToDevice)); }
-      HIP_TRY(hipMemcpy(dev.p[1], local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice));
-      rc = gcsa2_mem_hits_device(ix, static_cast<const u8*>(dev.p[0]), static_cast<const u64*>(dev.p[1]), count, bytes, min_length, hit_max, over,
-                                 static_cast<u64*>(dev.p[2]), static_cast<gcsa2_mem*>(dev.p[3]), rm, &m, static_cast<u64*>(dev.p[4]),
-                                 static_cast<u64*>(dev.p[5]), rh, &h, nullptr);
+      d_pat.release(); d_off.release(); d_mem_off.release(); d_mems.release(); d_hit_off.release(); d_hits.release();     // the piece before, the first attempt
+      HIP_TRY(d_pat.alloc(bytes + 16));
+      HIP_TRY(d_off.alloc(count + 1));
+      HIP_TRY(d_mem_off.alloc(count + 1));
+      HIP_TRY(d_mems.alloc(rm));
+      HIP_TRY(d_hit_off.alloc(rm + 1));
+      HIP_TRY(d_hits.alloc(rh));
+      if(bytes > 0) { HIP_TRY(hipMemcpy(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice)); }
+      HIP_TRY(hipMemcpy(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice));
+      rc = gcsa2_mem_hits_device(ix, d_pat.p, d_off.p, count, bytes, min_length, hit_max, over, d_mem_off.p, d_mems.p, rm, &m, d_hit_off.p, d_hits.p, rh, &h, nullptr);
       if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && m <= mem_room && h <= hit_room && (m > rm || h > rh)) { rm = m; rh = h; continue; }
       break;
     }
@@ -5010,13 +4744,13 @@ int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const u
     else if(rc != GCSA2_OK) { return rc; }
     else if(!exceeded)
     {
-      HIP_TRY(hipMemcpy(local.data(), dev.p[2], (count + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(local.data(), d_mem_off.p, (count + 1) * sizeof(u64), hipMemcpyDeviceToHost));
       for(u64 i = 0; i <= count; i++) { mem_offsets[b + i] = local[i] + mbase; }
-      if(m > 0) { HIP_TRY(hipMemcpy(mems + mbase, dev.p[3], m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
+      if(m > 0) { HIP_TRY(hipMemcpy(mems + mbase, d_mems.p, m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
       local.resize(m + 1);
-      HIP_TRY(hipMemcpy(local.data(), dev.p[4], (m + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(local.data(), d_hit_off.p, (m + 1) * sizeof(u64), hipMemcpyDeviceToHost));
       for(u64 i = 0; i <= m; i++) { hit_offsets[mbase + i] = local[i] + hbase; }
-      if(h > 0) { HIP_TRY(hipMemcpy(hits + hbase, dev.p[5], h * sizeof(u64), hipMemcpyDeviceToHost)); }
+      if(h > 0) { HIP_TRY(hipMemcpy(hits + hbase, d_hits.p, h * sizeof(u64), hipMemcpyDeviceToHost)); }
     }
     mbase += m;
     hbase += h;
@@ -5190,34 +4924,28 @@ int gcsa2_sub_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   try {   // no C++ exception may cross the C boundary
   DeviceGuard guard(ix->device);
   g_error.clear();
-  struct Dev
-  {
-    void* p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Dev() { for(void*& x : p) { if(x) { (void)hipFree(x); x = nullptr; } } }
-  } dev;
+  DBuf<u8> d_pat; DBuf<u64> d_off, d_mem_off, d_sub_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_mems, d_subs;
   const u64 bytes = offsets[nq];
-  HIP_TRY(hipMalloc(&dev.p[0], bytes + 16));
-  HIP_TRY(hipMalloc(&dev.p[1], (nq + 1) * sizeof(u64)));
-  HIP_TRY(hipMalloc(&dev.p[2], (nq + 1) * sizeof(u64)));
-  HIP_TRY(hipMalloc(&dev.p[3], n_mems * sizeof(gcsa2_mem)));
-  HIP_TRY(hipMalloc(&dev.p[4], (n_mems + 1) * sizeof(u64)));
-  HIP_TRY(hipMalloc(&dev.p[5], std::max<u64>(sub_capacity, 1) * sizeof(gcsa2_mem)));
-  HIP_TRY(hipMalloc(&dev.p[6], (sub_capacity + 1) * sizeof(u64)));
-  HIP_TRY(hipMalloc(&dev.p[7], std::max<u64>(hit_capacity, 1) * sizeof(u64)));
-  if(bytes > 0) { HIP_TRY(hipMemcpy(dev.p[0], patterns, bytes, hipMemcpyHostToDevice)); }
-  HIP_TRY(hipMemcpy(dev.p[1], offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dev.p[2], mem_offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dev.p[3], mems, n_mems * sizeof(gcsa2_mem), hipMemcpyHostToDevice));
-  rc = gcsa2_sub_mem_hits_device(ix, static_cast<const u8*>(dev.p[0]), static_cast<const u64*>(dev.p[1]), nq, bytes, static_cast<const u64*>(dev.p[2]),
-                                 static_cast<const gcsa2_mem*>(dev.p[3]), n_mems, min_length, reseed_length, hit_max, over,
-                                 static_cast<u64*>(dev.p[4]), static_cast<gcsa2_mem*>(dev.p[5]), sub_capacity, total_subs,
-                                 static_cast<u64*>(dev.p[6]), static_cast<u64*>(dev.p[7]), hit_capacity, total_hits, nullptr);
+  HIP_TRY(d_pat.alloc(bytes + 16));
+  HIP_TRY(d_off.alloc(nq + 1));
+  HIP_TRY(d_mem_off.alloc(nq + 1));
+  HIP_TRY(d_mems.alloc(n_mems));
+  HIP_TRY(d_sub_off.alloc(n_mems + 1));
+  HIP_TRY(d_subs.alloc(sub_capacity));
+  HIP_TRY(d_hit_off.alloc(sub_capacity + 1));
+  HIP_TRY(d_hits.alloc(hit_capacity));
+  if(bytes > 0) { HIP_TRY(hipMemcpy(d_pat.p, patterns, bytes, hipMemcpyHostToDevice)); }
+  HIP_TRY(hipMemcpy(d_off.p, offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_mem_off.p, mem_offsets, (nq + 1) * sizeof(u64), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_mems.p, mems, n_mems * sizeof(gcsa2_mem), hipMemcpyHostToDevice));
+  rc = gcsa2_sub_mem_hits_device(ix, d_pat.p, d_off.p, nq, bytes, d_mem_off.p, d_mems.p, n_mems, min_length, reseed_length, hit_max, over,
+                                 d_sub_off.p, d_subs.p, sub_capacity, total_subs, d_hit_off.p, d_hits.p, hit_capacity, total_hits, nullptr);
   if(rc != GCSA2_OK) { return rc; }
   const u64 s = *total_subs, h = *total_hits;
-  HIP_TRY(hipMemcpy(sub_offsets, dev.p[4], (n_mems + 1) * sizeof(u64), hipMemcpyDeviceToHost));
-  if(s > 0) { HIP_TRY(hipMemcpy(subs, dev.p[5], s * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
-  HIP_TRY(hipMemcpy(hit_offsets, dev.p[6], (s + 1) * sizeof(u64), hipMemcpyDeviceToHost));
-  if(h > 0) { HIP_TRY(hipMemcpy(hits, dev.p[7], h * sizeof(u64), hipMemcpyDeviceToHost)); }
+  HIP_TRY(hipMemcpy(sub_offsets, d_sub_off.p, (n_mems + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+  if(s > 0) { HIP_TRY(hipMemcpy(subs, d_subs.p, s * sizeof(gcsa2_mem), hipMemcpyDeviceToHost)); }
+  HIP_TRY(hipMemcpy(hit_offsets, d_hit_off.p, (s + 1) * sizeof(u64), hipMemcpyDeviceToHost));
+  if(h > 0) { HIP_TRY(hipMemcpy(hits, d_hits.p, h * sizeof(u64), hipMemcpyDeviceToHost)); }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_sub_mem_hits_batch: ") + e.what()); }
 }
