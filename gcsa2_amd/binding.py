@@ -39,7 +39,8 @@ EXPORTS = [
     "gcsa2_group_find_batch", "gcsa2_group_find_device", "gcsa2_group_uses_rccl",
     "gcsa2_group_match_stats_device", "gcsa2_group_locate_device", "gcsa2_comm_match_stats", "gcsa2_comm_locate",
     "gcsa2_comm_unique_id", "gcsa2_comm_create", "gcsa2_comm_create_custom", "gcsa2_comm_destroy", "gcsa2_comm_rank", "gcsa2_comm_world", "gcsa2_comm_rccl_ranks", "gcsa2_comm_gather",
-    "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
+    "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch",
+    "gcsa2_match_breaks_bounded_device", "gcsa2_match_breaks_bounded_batch", "gcsa2_mem_hits_bounded_device", "gcsa2_mem_hits_bounded_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -151,6 +152,10 @@ def load_library():
     L.gcsa2_match_breaks_device.argtypes = [vp, vp, vp, u64, u64, i32, u64, vp, vp, u64, u64p, vp, vp, vp]
     L.gcsa2_mem_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_match_breaks_bounded_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64p, vp, u64, u64p, vp, vp]
+    L.gcsa2_match_breaks_bounded_device.argtypes = [vp, vp, vp, u64, u64, i32, u64, u64, vp, vp, u64, u64p, vp, vp, vp]
+    L.gcsa2_mem_hits_bounded_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
+    L.gcsa2_mem_hits_bounded_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_sub_mem_hits_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_sub_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64p, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -572,11 +577,12 @@ class GCSA:
             _check(self._L.gcsa2_match_stats_device_sized(self._h, variant, d_patterns, d_offsets, nq, int(total_bytes), d_ms, d_ranges,
                                                           d_fallbacks, stream))
 
-    def match_breaks_batch(self, patterns, offsets, min_length=0, capacity=None, out=None):
+    def match_breaks_batch(self, patterns, offsets, min_length=0, capacity=None, out=None, max_length=0):
         """Break points of a batch in host memory: (break_offsets (nq + 1), breaks (total, 4) = {position, length, sp, ep}, ranges,
         parent() counts).  The record buffer is sized from the refusal when `capacity` is too small (default: 4 per pattern).
         `out` = (break_offsets, breaks, ranges, fallbacks) arrays of the caller (a caller that reuses them avoids the page faults
-        of fresh ones); too few rows in `breaks` raise BUFFER_TOO_SMALL with `needed`."""
+        of fresh ones); too few rows in `breaks` raise BUFFER_TOO_SMALL with `needed`.  max_length > 0: no match grows beyond
+        that many characters (gcsa2_match_breaks_bounded_batch; a mapper passes order()); 0: no cap."""
         patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nq = offsets.shape[0] - 1
@@ -585,7 +591,7 @@ class GCSA:
             assert boff.dtype == np.uint64 and boff.shape[0] >= nq + 1 and brk.dtype == np.uint64 and brk.flags.c_contiguous and brk.shape[1] == 4
             assert rng.dtype == np.uint64 and rng.shape[0] >= nq and fb.dtype == np.uint64 and fb.shape[0] >= nq
             total = C.c_uint64()
-            rc = self._L.gcsa2_match_breaks_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), _p64(boff), brk.ctypes.data, brk.shape[0],
+            rc = self._L.gcsa2_match_breaks_bounded_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), int(max_length), _p64(boff), brk.ctypes.data, brk.shape[0],
                                                   C.byref(total), rng.ctypes.data, fb.ctypes.data)
             if rc == -6:
                 err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
@@ -600,7 +606,7 @@ class GCSA:
         total = C.c_uint64()
         for _ in range(2):
             brk = np.zeros((max(cap, 1), 4), dtype=np.uint64)
-            rc = self._L.gcsa2_match_breaks_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), _p64(boff), brk.ctypes.data, cap,
+            rc = self._L.gcsa2_match_breaks_bounded_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), int(max_length), _p64(boff), brk.ctypes.data, cap,
                                                   C.byref(total), rng.ctypes.data, fb.ctypes.data)
             if rc == -6 and total.value > cap:
                 cap = total.value
@@ -610,13 +616,13 @@ class GCSA:
         _check(rc)
 
     def match_breaks_device(self, d_patterns, d_offsets, nq, total_bytes, d_break_offsets, d_breaks, capacity, d_ranges=0, d_fallbacks=0,
-                            stream=0, variant=0, min_length=0):
+                            stream=0, variant=0, min_length=0, max_length=0):
         """Matching statistics as break points (gcsa2_match_breaks_device): the CSR of the left-maximal matches, records of four
         u64 {position, length, sp, ep}; returns the number of records.  Raises Gcsa2Error (BUFFER_TOO_SMALL, `.needed`) when
-        `capacity` records are not enough."""
+        `capacity` records are not enough.  max_length > 0 caps the matches (gcsa2_match_breaks_bounded_device)."""
         total = C.c_uint64()
         tb = 0xFFFFFFFFFFFFFFFF if total_bytes is None else int(total_bytes)
-        rc = self._L.gcsa2_match_breaks_device(self._h, d_patterns, d_offsets, nq, tb, variant, int(min_length), d_break_offsets, d_breaks, capacity, C.byref(total),
+        rc = self._L.gcsa2_match_breaks_bounded_device(self._h, d_patterns, d_offsets, nq, tb, variant, int(min_length), int(max_length), d_break_offsets, d_breaks, capacity, C.byref(total),
                                                d_ranges, d_fallbacks, stream)
         if rc != 0:
             err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
@@ -624,12 +630,12 @@ class GCSA:
             raise err
         return total.value
 
-    def mem_hits_batch(self, patterns, offsets, min_length, hit_max=0, sample=False, out=None):
+    def mem_hits_batch(self, patterns, offsets, min_length, hit_max=0, sample=False, out=None, max_length=0):
         """MEM hits of a batch in host memory (gcsa2_mem_hits_batch): (mem_offsets (nq + 1), mems (total, 5) = {position, length,
         sp, ep, count}, hit_offsets (total + 1), hits).  A MEM's hits are its locate() values when hit_max == 0 or its count is at
         most hit_max; above the cap none (sample=False) or locate(range, hit_max) (sample=True).  The buffers are grown from the
         refusal.  `out` = (mem_offsets, mems, hit_offsets, hits) arrays of the caller; too small ones raise BUFFER_TOO_SMALL with
-        `needed` = (MEMs, hits)."""
+        `needed` = (MEMs, hits).  max_length > 0: the MEMs of match_breaks_batch(max_length=...) (gcsa2_mem_hits_bounded_batch)."""
         patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         nq = offsets.shape[0] - 1
@@ -639,7 +645,7 @@ class GCSA:
         def call(moff, mems, hoff, hits):
             assert moff.dtype == np.uint64 and moff.shape[0] >= nq + 1 and mems.dtype == np.uint64 and mems.flags.c_contiguous
             assert mems.shape[1] == 5 and hoff.dtype == np.uint64 and hoff.shape[0] >= mems.shape[0] + 1 and hits.dtype == np.uint64
-            return self._L.gcsa2_mem_hits_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), int(hit_max), over,
+            return self._L.gcsa2_mem_hits_bounded_batch(self._h, _p8(patterns), _p64(offsets), nq, int(min_length), int(max_length), int(hit_max), over,
                                                 moff.ctypes.data, mems.ctypes.data, mems.shape[0], C.byref(total_m),
                                                 hoff.ctypes.data, hits.ctypes.data, hits.shape[0], C.byref(total_h))
 
@@ -666,14 +672,15 @@ class GCSA:
         return moff[: nq + 1], mems[:m], hoff[: m + 1], hits[:h]
 
     def mem_hits_device(self, d_patterns, d_offsets, nq, total_bytes, min_length, hit_max, sample, d_mem_offsets, d_mems, mem_capacity,
-                        d_hit_offsets, d_hits, hit_capacity, stream=0):
+                        d_hit_offsets, d_hits, hit_capacity, stream=0, max_length=0):
         """MEM hits into caller-owned device buffers (gcsa2_mem_hits_device): d_mems holds mem_capacity records of five u64,
         d_hit_offsets mem_capacity + 1 entries, d_hits hit_capacity values; total_bytes None = read back.  Returns (MEMs, hits);
-        raises Gcsa2Error (BUFFER_TOO_SMALL, `.needed` = (MEMs, hits)) when a buffer is too small."""
+        raises Gcsa2Error (BUFFER_TOO_SMALL, `.needed` = (MEMs, hits)) when a buffer is too small.  max_length > 0 caps the
+        matches (gcsa2_mem_hits_bounded_device)."""
         total_m, total_h = C.c_uint64(), C.c_uint64()
         tb = 0xFFFFFFFFFFFFFFFF if total_bytes is None else int(total_bytes)
         over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
-        rc = self._L.gcsa2_mem_hits_device(self._h, d_patterns, d_offsets, nq, tb, int(min_length), int(hit_max), over, d_mem_offsets,
+        rc = self._L.gcsa2_mem_hits_bounded_device(self._h, d_patterns, d_offsets, nq, tb, int(min_length), int(max_length), int(hit_max), over, d_mem_offsets,
                                            d_mems, mem_capacity, C.byref(total_m), d_hit_offsets, d_hits, hit_capacity, C.byref(total_h),
                                            stream)
         if rc != 0:

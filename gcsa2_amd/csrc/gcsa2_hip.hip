@@ -3499,7 +3499,17 @@ int match_stats_launch(const gcsa2_index* ix, int variant, const uint8_t* d_patt
     if(qe != hipSuccess) { (void)hipFreeAsync(recs, st); return fail(GCSA2_ERR_HIP, std::string("matching statistics queue: ") + hipGetErrorString(qe)); }
     const unsigned grid = unsigned(lanes_grid < resident ? lanes_grid : resident);
     unsigned long long* none = nullptr;
-    if(sink != nullptr && pair)
+    if(sink != nullptr && sink->max_length != 0 && pair)
+    {
+      hipLaunchKernelGGL((k_match_stats2<true, true, false, true, true>), dim3(grid), dim3(TPB2), 0, st,
+                         ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, queue, ix->tune.ms_refill_at, recs, none, *sink);
+    }
+    else if(sink != nullptr && sink->max_length != 0)
+    {
+      hipLaunchKernelGGL((k_match_stats2<false, true, false, true, true>), dim3(grid), dim3(TPB2), 0, st,
+                         ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, queue, ix->tune.ms_refill_at, recs, none, *sink);
+    }
+    else if(sink != nullptr && pair)
     {
       hipLaunchKernelGGL((k_match_stats2<true, true, false, true>), dim3(grid), dim3(TPB2), 0, st,
                          ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, queue, ix->tune.ms_refill_at, recs, none, *sink);
@@ -3523,7 +3533,17 @@ int match_stats_launch(const gcsa2_index* ix, int variant, const uint8_t* d_patt
   else if(sink != nullptr)
   {
     unsigned long long* none = nullptr;
-    if(pair)
+    if(sink->max_length != 0 && pair)
+    {
+      hipLaunchKernelGGL((k_match_stats2<true, false, false, true, true>), dim3(unsigned(lanes_grid)), dim3(TPB2), 0, st,
+                         ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, none, 64u, recs, none, *sink);
+    }
+    else if(sink->max_length != 0)
+    {
+      hipLaunchKernelGGL((k_match_stats2<false, false, false, true, true>), dim3(unsigned(lanes_grid)), dim3(TPB2), 0, st,
+                         ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, none, 64u, recs, none, *sink);
+    }
+    else if(pair)
     {
       hipLaunchKernelGGL((k_match_stats2<true, false, false, true>), dim3(unsigned(lanes_grid)), dim3(TPB2), 0, st,
                          ix->img, d_patterns, d_offsets, nq, out, d_ranges, d_fallbacks, cool, none, 64u, recs, none, *sink);
@@ -3566,11 +3586,20 @@ extern "C" int gcsa2_match_stats_device(const gcsa2_index* ix, const uint8_t* d_
 
 // Matching statistics as BREAK POINTS (k_match_stats2<.., BREAKS>): the CSR of the left-maximal matches of every pattern.
 // Complete on return: the number of records is read back, and a buffer that is too small is refused with the number needed.
-int gcsa2_match_breaks_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_bytes,
-                              int variant, uint64_t min_length, uint64_t* d_break_offsets, gcsa2_break* d_breaks, uint64_t capacity, uint64_t* total_breaks,
-                              uint64_t* d_ranges, uint64_t* d_fallbacks, void* stream)
+// max_length > 0: no match grows beyond that many characters (k_match_stats2<.., CAP>); 0, or a value no pattern reaches: no cap.
+namespace {
+inline u64 effective_cap(u64 max_length) { return max_length >= (u64(1) << 32) ? 0 : max_length; }   // (a pattern is shorter than 2^32 characters)
+#define CHECK_CAP(min_length, max_length) \
+  do { if(effective_cap(max_length) != 0 && (min_length) > (max_length)) \
+       { return fail(GCSA2_ERR_INVALID_ARGUMENT, "min_length exceeds max_length: no match could be reported"); } } while(0)
+}  // namespace
+
+int gcsa2_match_breaks_bounded_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_bytes,
+                                      int variant, uint64_t min_length, uint64_t max_length, uint64_t* d_break_offsets, gcsa2_break* d_breaks,
+                                      uint64_t capacity, uint64_t* total_breaks, uint64_t* d_ranges, uint64_t* d_fallbacks, void* stream)
 {
   CHECK_INDEX(ix);
+  CHECK_CAP(min_length, max_length);
   if(d_break_offsets == nullptr || total_breaks == nullptr || (d_breaks == nullptr && capacity > 0)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
   if(nq >= (u64(1) << 31) - 1) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "batch of >= 2^31 patterns; split the batch"); }
   DeviceGuard guard(ix->device);
@@ -3595,7 +3624,7 @@ int gcsa2_match_breaks_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
   const u64 waves = (persistent && resident * (TPB2 / 64) < lane_waves ? resident * (TPB2 / 64) : lane_waves);
   const u64 most = (total_bytes != GCSA2_UNKNOWN && total_bytes + nq < capacity ? total_bytes + nq : capacity);
   const u64 tmp_slots = most + (waves + 1) * BREAK_BLOCK;
-  BreakSink sink{nullptr, tmp_slots, nullptr, nullptr, u32(min_length > 0xFFFFFFFFull ? 0xFFFFFFFFull : min_length)};
+  BreakSink sink{nullptr, tmp_slots, nullptr, nullptr, u32(min_length > 0xFFFFFFFFull ? 0xFFFFFFFFull : min_length), u32(effective_cap(max_length))};
   u64 *wide = nullptr, *own_ranges = nullptr;
   const unsigned slot = ix->next_slot.fetch_add(1) % RESULT_SLOTS;
   unsigned long long* d_totals = ix->d_slots + u64(TOTAL_WORDS) * slot;
@@ -3648,6 +3677,14 @@ int gcsa2_match_breaks_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
   return GCSA2_OK;
 }
 
+int gcsa2_match_breaks_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_bytes,
+                              int variant, uint64_t min_length, uint64_t* d_break_offsets, gcsa2_break* d_breaks, uint64_t capacity, uint64_t* total_breaks,
+                              uint64_t* d_ranges, uint64_t* d_fallbacks, void* stream)
+{
+  return gcsa2_match_breaks_bounded_device(ix, d_patterns, d_offsets, nq, total_bytes, variant, min_length, 0, d_break_offsets, d_breaks, capacity,
+                                           total_breaks, d_ranges, d_fallbacks, stream);
+}
+
 namespace {
 
 // The break points of a large host batch, in pieces like the dense statistics of match_stats_pieced (a MEM finder's reads live in host memory:
@@ -3657,7 +3694,7 @@ namespace {
 // kernel at most), takes its place and downloads there.  The device-side record buffer of a piece is sized by an estimate
 // (one record per 8 pattern bytes; a piece that needs more runs again with the exact size).  Once the caller's capacity is
 // exceeded the remaining pieces only count: GCSA2_ERR_BUFFER_TOO_SMALL with the number of records of the whole batch.
-int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length, uint64_t max_length,
                         uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks)
 {
   const std::vector<u64> cut = cut_pieces(offsets, nq, ix->tune.ms_piece_bytes);
@@ -3693,7 +3730,7 @@ int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const ui
         e = lease.up(d_pat, patterns + first, bytes);
         if(e == hipSuccess) { e = lease.up(d_off, local.data(), (count + 1) * sizeof(u64)); }
         if(e != hipSuccess) { give_up(GCSA2_ERR_HIP, std::string("upload of a piece: ") + hipGetErrorString(e)); break; }
-        const int rc = gcsa2_match_breaks_device(ix, d_pat, d_off, count, bytes, 0, min_length, d_boff, d_brk, room, &found, d_rng, d_fb, lease.stream());
+        const int rc = gcsa2_match_breaks_bounded_device(ix, d_pat, d_off, count, bytes, 0, min_length, max_length, d_boff, d_brk, room, &found, d_rng, d_fb, lease.stream());
         if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && found > room) { room = found; (void)lease.finish(); continue; }    // the estimate was short: once more, exactly
         if(rc != GCSA2_OK) { give_up(rc, g_error); break; }
         // commit in piece order: the position of this piece's first record
@@ -3730,12 +3767,13 @@ int match_breaks_pieced(const gcsa2_index* ix, const uint8_t* patterns, const ui
 
 }  // namespace
 
-// The break points of a batch in host memory: one copy in, gcsa2_match_breaks_device, the CSR out.
-int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
-                             uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks,
-                             uint64_t* ranges, uint64_t* fallbacks)
+// The break points of a batch in host memory: one copy in, gcsa2_match_breaks_bounded_device, the CSR out.
+int gcsa2_match_breaks_bounded_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                                     uint64_t max_length, uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks,
+                                     uint64_t* ranges, uint64_t* fallbacks)
 {
   CHECK_INDEX(ix);
+  CHECK_CAP(min_length, max_length);
   if(nq == 0)             // an empty batch: no records, whatever the (possibly null) input arrays are
   {
     if(total_breaks != nullptr) { *total_breaks = 0; }
@@ -3753,7 +3791,7 @@ int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   {
     if(ix->tune.ms_pieces && offsets[nq] >= 2 * ix->tune.ms_piece_bytes && longest <= ix->tune.ms_piece_bytes)
     {
-      return match_breaks_pieced(ix, patterns, offsets, nq, min_length, break_offsets, breaks, capacity, total_breaks, ranges, fallbacks);
+      return match_breaks_pieced(ix, patterns, offsets, nq, min_length, max_length, break_offsets, breaks, capacity, total_breaks, ranges, fallbacks);
     }
     DeviceGuard guard(ix->device);
     const u64 total = offsets[nq];
@@ -3765,7 +3803,7 @@ int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, con
     u64* d_rng = lease.dev<u64>(2 * nq); u64* d_fb = lease.dev<u64>(nq);
     HIP_TRY(lease.up(d_pat, patterns, total));
     HIP_TRY(lease.up(d_off, offsets, (nq + 1) * sizeof(u64)));
-    int rc = gcsa2_match_breaks_device(ix, d_pat, d_off, nq, total, 0, min_length, d_boff, d_brk, capacity, total_breaks, d_rng, d_fb, lease.stream());
+    int rc = gcsa2_match_breaks_bounded_device(ix, d_pat, d_off, nq, total, 0, min_length, max_length, d_boff, d_brk, capacity, total_breaks, d_rng, d_fb, lease.stream());
     if(rc != GCSA2_OK) { return rc; }
     HIP_TRY(lease.down(break_offsets, d_boff, (nq + 1) * sizeof(u64)));
     if(*total_breaks > 0) { HIP_TRY(lease.down(breaks, d_brk, *total_breaks * sizeof(gcsa2_break))); }
@@ -3775,6 +3813,13 @@ int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, con
     return GCSA2_OK;
   }
   catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_match_breaks_batch: ") + e.what()); }
+}
+
+int gcsa2_match_breaks_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                             uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity, uint64_t* total_breaks,
+                             uint64_t* ranges, uint64_t* fallbacks)
+{
+  return gcsa2_match_breaks_bounded_batch(ix, patterns, offsets, nq, min_length, 0, break_offsets, breaks, capacity, total_breaks, ranges, fallbacks);
 }
 
 // Diagnostic: the default kernel instrumented with shader-clock counters per phase of its round (k_match_stats2<.., PROF>),
@@ -4519,7 +4564,7 @@ int mem_hits_tail(const gcsa2_index* ix, const u64* brk, const u64* known, u64 m
 
 // gcsa2_mem_hits_device after its argument checks (nq > 0).  Host round trips: the pattern bytes (only when the caller does
 // not know them), the break total (inside gcsa2_match_breaks_device), the class totals, those of the locate passes, the end.
-int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 nq, u64 total_bytes, u64 min_length,
+int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 nq, u64 total_bytes, u64 min_length, u64 max_length,
                   u64 hit_max, int over, u64* d_mem_offsets, gcsa2_mem* d_mems, u64 mem_capacity, u64* total_mems,
                   u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
 {
@@ -4536,14 +4581,14 @@ int mem_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64
   u64* brk = nullptr;
   u64 m = 0;
   HIP_TRY(scratch.get(brk, 4 * room));
-  int rc = gcsa2_match_breaks_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
+  int rc = gcsa2_match_breaks_bounded_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, max_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
                                      room, &m, nullptr, nullptr, st);
   if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && m > room)
   {
     room = m;
     HIP_TRY(scratch.get(brk, 4 * room));
     g_error.clear();
-    rc = gcsa2_match_breaks_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
+    rc = gcsa2_match_breaks_bounded_device(ix, d_patterns, d_offsets, nq, total_bytes, 0, min_length, max_length, d_mem_offsets, reinterpret_cast<gcsa2_break*>(brk),
                                    room, &m, nullptr, nullptr, st);
   }
   if(rc != GCSA2_OK) { return rc; }
@@ -4656,11 +4701,13 @@ int mem_hits_tail(const gcsa2_index* ix, const u64* brk, const u64* known, u64 m
 
 extern "C" {
 
-int gcsa2_mem_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_pattern_bytes,
-                          uint64_t min_length, uint64_t hit_max, int over, uint64_t* d_mem_offsets, gcsa2_mem* d_mems, uint64_t mem_capacity,
-                          uint64_t* total_mems, uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+int gcsa2_mem_hits_bounded_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_pattern_bytes,
+                                  uint64_t min_length, uint64_t max_length, uint64_t hit_max, int over, uint64_t* d_mem_offsets, gcsa2_mem* d_mems,
+                                  uint64_t mem_capacity, uint64_t* total_mems, uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity,
+                                  uint64_t* total_hits, void* stream)
 {
   CHECK_INDEX(ix);
+  CHECK_CAP(min_length, max_length);
   if(total_mems == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
   *total_mems = 0;
   *total_hits = 0;
@@ -4682,20 +4729,29 @@ int gcsa2_mem_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, cons
     HIP_TRY(hipStreamSynchronize(st));
     return GCSA2_OK;
   }
-  return mem_hits_core(ix, d_patterns, d_offsets, nq, total_pattern_bytes, min_length, hit_max, over, d_mem_offsets, d_mems, mem_capacity,
+  return mem_hits_core(ix, d_patterns, d_offsets, nq, total_pattern_bytes, min_length, max_length, hit_max, over, d_mem_offsets, d_mems, mem_capacity,
                        total_mems, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_mem_hits_device: ") + e.what()); }
+}
+
+int gcsa2_mem_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t nq, uint64_t total_pattern_bytes,
+                          uint64_t min_length, uint64_t hit_max, int over, uint64_t* d_mem_offsets, gcsa2_mem* d_mems, uint64_t mem_capacity,
+                          uint64_t* total_mems, uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  return gcsa2_mem_hits_bounded_device(ix, d_patterns, d_offsets, nq, total_pattern_bytes, min_length, 0, hit_max, over, d_mem_offsets, d_mems,
+                                       mem_capacity, total_mems, d_hit_offsets, d_hits, hit_capacity, total_hits, stream);
 }
 
 // The host form: pieces of tune.ms_piece_bytes pattern bytes (a batch of two pieces' worth or more; one piece otherwise), each
 // copied in, run through gcsa2_mem_hits_device and copied out behind the pieces before it.  A piece's device buffers are sized
 // from the caller's remaining room (one piece) or an estimate (a piece that needs more runs again with the exact sizes); once
-// the caller's room is exceeded the remaining pieces only count.
-int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
-                         uint64_t hit_max, int over, uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
-                         uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
+// the caller's room is exceeded the remaining pieces only count.  Every piece runs under the same max_length.
+int gcsa2_mem_hits_bounded_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                                 uint64_t max_length, uint64_t hit_max, int over, uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity,
+                                 uint64_t* total_mems, uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
 {
   CHECK_INDEX(ix);
+  CHECK_CAP(min_length, max_length);
   if(total_mems == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
   *total_mems = 0;
   *total_hits = 0;
@@ -4736,7 +4792,7 @@ int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const u
       HIP_TRY(d_hits.alloc(rh));
       if(bytes > 0) { HIP_TRY(hipMemcpy(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice)); }
       HIP_TRY(hipMemcpy(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice));
-      rc = gcsa2_mem_hits_device(ix, d_pat.p, d_off.p, count, bytes, min_length, hit_max, over, d_mem_off.p, d_mems.p, rm, &m, d_hit_off.p, d_hits.p, rh, &h, nullptr);
+      rc = gcsa2_mem_hits_bounded_device(ix, d_pat.p, d_off.p, count, bytes, min_length, max_length, hit_max, over, d_mem_off.p, d_mems.p, rm, &m, d_hit_off.p, d_hits.p, rh, &h, nullptr);
       if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && m <= mem_room && h <= hit_room && (m > rm || h > rh)) { rm = m; rh = h; continue; }
       break;
     }
@@ -4763,6 +4819,14 @@ int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const u
   }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_mem_hits_batch: ") + e.what()); }
+}
+
+int gcsa2_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t nq, uint64_t min_length,
+                         uint64_t hit_max, int over, uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
+                         uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
+{
+  return gcsa2_mem_hits_bounded_batch(ix, patterns, offsets, nq, min_length, 0, hit_max, over, mem_offsets, mems, mem_capacity, total_mems,
+                                      hit_offsets, hits, hit_capacity, total_hits);
 }
 
 }  // extern "C"

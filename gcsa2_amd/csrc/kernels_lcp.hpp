@@ -554,15 +554,21 @@ constexpr u64 MS_REFILL_MIN = u64(1) << 19;             // host-pointer API: sma
 // final record and the end of the pattern are deferred by one round (a lane writes one record per round).  The order matters:
 // need_parent, pending and last_break are read after the step; moving the record back to the loop head reports the state of
 // the NEXT match.  Exactly the positions p with p == 0 or ms[p - 1] != ms[p] + 1 get a record.
+// CAP = true (gcsa2_match_breaks_bounded_device with max_length > 0; BREAKS only): no match grows beyond sink.max_length
+// characters.  A lane whose depth has reached the cap is planned as if its next step had failed already -- plan_and_issue()
+// sets need_parent, so the lane asks for its LCP window and for no rank block, and the record logic behind it, which reads
+// need_parent, writes the break of the capped match in the same round: a capped position costs the round of its parent() and
+// nothing else.  A pair step needs room for two characters, and the k-mer seed is taken only if it fits under the cap.
 struct BreakSink
 {
   u64* tmp; u64 cap; unsigned long long* counter; u32* counts; u32 min_length;
+  u32 max_length;                            // CAP only (in the struct's tail padding: the argument segment keeps its layout)
 };
 constexpr u32 BREAK_WORDS = 4;               // {pattern | ordinal << 32, position | length << 32, sp, ep}
 constexpr u32 BREAK_BLOCK = 256;             // record slots a wavefront reserves at a time
 constexpr u64 BREAK_HOLE = ~u64(0);          // pattern field of an unused slot (the tail of a wave's last block)
 
-template<bool PAIR, bool REFILL, bool PROF = false, bool BREAKS = false>
+template<bool PAIR, bool REFILL, bool PROF = false, bool BREAKS = false, bool CAP = false>
 __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8* __restrict__ patterns,
                                                        const u64* __restrict__ offsets, u64 nq,
                                                        unsigned short* __restrict__ ms, u64* __restrict__ ranges,
@@ -571,6 +577,7 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
                                                        const ulonglong2* __restrict__ recs,
                                                        unsigned long long* __restrict__ prof = nullptr, BreakSink sink = BreakSink{nullptr, 0, nullptr, nullptr, 0})
 {
+  static_assert(!CAP || BREAKS, "the cap exists for the break records only");
   [[maybe_unused]] u64 prof_t = 0, prof_c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   [[maybe_unused]] u32 prof_n[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr(PROF) { prof_t = clock64(); }
@@ -613,6 +620,8 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
   // re-read from the argument segment -- an s_load and a full s_waitcnt -- in every round of every wave: +10 % on the batch)
   [[maybe_unused]] u32 min_length = sink.min_length;
   if constexpr(BREAKS) { asm volatile("" : "+v"(min_length)); }
+  [[maybe_unused]] u32 max_length = sink.max_length;           // CAP: in a vector register for the same reason (read in every round)
+  if constexpr(CAP) { asm volatile("" : "+v"(max_length)); }
   // (The record buffer's address and capacity stay kernel arguments: they are read only where a record is written.  Holding
   // them in vector registers as well -- 127 VGPRs -- cost the persistent form 2.9 ms on config 5's batch; profiles/r04_match_stats.md.)
   [[maybe_unused]] bool pending = false;                       // BREAKS: a character that does not occur: position i is a break of length 0
@@ -665,7 +674,9 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
     // are 1 .. k -- and skips the steps on the widest ranges, whose endpoints lie in different blocks.  An empty or wide
     // entry starts from scratch.
     const u32 k = img.kmer_k;
-    if(k > 0 && total >= k && img.n > 0)
+    bool seed = (k > 0 && total >= k && img.n > 0);
+    if constexpr(CAP) { seed = seed && k <= max_length; }       // (a seed longer than the cap: from the root)
+    if(seed)
     {
       const u64 tix = win_code & ((u64(1) << (2 * k)) - 1);
       const bool fast = (win_bad & ((1u << k) - 1)) == 0;
@@ -704,9 +715,15 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
   bool planned = false, pair = false;       // planned: this lane has a block (or LCP window) in flight
   u32 comp = 0, r_sp = 0, r_ep = 0, idx_sp = 0, idx_ep = 0, emit_code = 0;
   u64 wstart = 0;
-  auto plan_and_issue = [&]()
+  // (first: the call in front of the loop, which no record logic follows -- a lane that is at the cap already, through its seed,
+  // sits that request out and is planned by the first round's call, like a lane that has just drawn a pattern)
+  auto plan_and_issue = [&](bool first)
   {
-    const bool active = has && i > 0;
+    bool active = has && i > 0;
+    if constexpr(CAP)
+    {
+      if(active && !need_parent && depth >= max_length) { if(first) { active = false; } else { need_parent = true; } }
+    }
     planned = active;
     const bool stepping = active && !need_parent, parenting = active && need_parent;
     comp = 0; r_sp = 0; r_ep = 0; idx_sp = 0; idx_ep = 0; pair = false; wstart = 0;
@@ -722,7 +739,9 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
       const u32 flags = ((win_bad >> r) & 3) | (r == 31 ? (next_bad & 1) << 1 : 0u);
       if constexpr(PAIR)
       {
-        if(force_single == 0 && i >= 2)
+        bool fits = true;
+        if constexpr(CAP) { fits = depth + 2 <= max_length; }  // (at depth == max_length - 1 the lane steps singly)
+        if(force_single == 0 && i >= 2 && fits)
         {
           pair = (flags == 0);
           if(pair)
@@ -751,7 +770,7 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
 
     if(__any(active)) { fetch_blocks_issue<PAIR, true>(img.flb, idx_sp, active, wave_stage, lane, img.flp, img.lcp, wave_addr); }
   };
-  plan_and_issue();
+  plan_and_issue(true);
   while(true)
   {
     const bool active = planned;
@@ -830,7 +849,7 @@ __global__ __launch_bounds__(TPB2, 4) void k_match_stats2(DevImage img, const u8
     }
     G2_TICK(7);
     if(emit_code != 0) { consumed(emit_code); }                 // (one site: the characters this round consumed, 0..2)
-    plan_and_issue();                                            // the next round's requests leave here
+    plan_and_issue(false);                                       // the next round's requests leave here
     G2_TICK(1);
     if constexpr(!BREAKS)                                        // the statistics of the step just taken (positions i + 1 / i after the update)
     {

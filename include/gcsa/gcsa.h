@@ -168,6 +168,15 @@ public:
   void match_breaks_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type min_length,
                           std::vector<size_type>& offsets_out, std::vector<gcsa2_break>& breaks) const
   {
+    match_breaks_batch(patterns, offsets, min_length, 0, offsets_out, breaks);
+  }
+
+  // The same with a maximum match length (gcsa2_match_breaks_bounded_batch): a match that has reached max_length characters
+  // is cut as if the next character had failed, and the search goes on from parent().  The index answers for patterns up to
+  // its order (a longer one "may result in false positives"), so a mapper passes order(); 0 means no cap.
+  void match_breaks_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type min_length,
+                          size_type max_length, std::vector<size_type>& offsets_out, std::vector<gcsa2_break>& breaks) const
+  {
     const size_type nq = offsets.empty() ? 0 : offsets.size() - 1;
     offsets_out.assign(nq + 1, 0);
     if(nq == 0) { breaks.clear(); return; }                    // an empty batch: no records
@@ -176,8 +185,8 @@ public:
     size_type total = 0;
     for(int attempt = 0; attempt < 2; attempt++)
     {
-      const int rc = gcsa2_match_breaks_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.data(), nq, min_length, offsets_out.data(),
-                                              breaks.data(), breaks.size(), &total, nullptr, nullptr);
+      const int rc = gcsa2_match_breaks_bounded_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.data(), nq, min_length, max_length,
+                                                      offsets_out.data(), breaks.data(), breaks.size(), &total, nullptr, nullptr);
       if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && total > breaks.size()) { breaks.assign(total, gcsa2_break()); continue; }
       check(rc, "GCSA::match_breaks_batch()");
       break;
@@ -193,6 +202,15 @@ public:
                       size_type hit_max, bool sample, std::vector<size_type>& mem_offsets, std::vector<gcsa2_mem>& mems,
                       std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
   {
+    mem_hits_batch(patterns, offsets, min_length, 0, hit_max, sample, mem_offsets, mems, hit_offsets, hits);
+  }
+
+  // The same with a maximum match length (gcsa2_mem_hits_bounded_batch): the MEMs of the bounded match_breaks_batch.  A
+  // mapper passes order() -- beyond it the index may report matches the graph does not have; 0 means no cap.
+  void mem_hits_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type min_length,
+                      size_type max_length, size_type hit_max, bool sample, std::vector<size_type>& mem_offsets, std::vector<gcsa2_mem>& mems,
+                      std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
     const size_type nq = offsets.empty() ? 0 : offsets.size() - 1;
     mem_offsets.assign(nq + 1, 0);
     mems.assign(4 * nq + 16, gcsa2_mem());
@@ -202,8 +220,8 @@ public:
     for(int attempt = 0; attempt < 2; attempt++)
     {
       hit_offsets.assign(mems.size() + 1, 0);
-      const int rc = gcsa2_mem_hits_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), nq,
-                                          min_length, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, mem_offsets.data(), mems.data(),
+      const int rc = gcsa2_mem_hits_bounded_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), nq,
+                                          min_length, max_length, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, mem_offsets.data(), mems.data(),
                                           mems.size(), &total_mems, hit_offsets.data(), hits.data(), hits.size(), &total_hits);
       if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0)
       {

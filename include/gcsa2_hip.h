@@ -398,7 +398,9 @@ int gcsa2_compare_kmers_records(const gcsa2_index* left, const gcsa2_index* righ
  * replaced by its parent and the character retried; at the root the character is skipped.
  * ms[offsets[q] + i] = length of the longest match starting at byte i of pattern q that the
  * index reports (capped at 65535; exact for lengths <= order()), ranges[2q..] = range of that
- * match for i = 0, fallbacks[q] = number of parent() calls (may be NULL).  Needs the LCP array. */
+ * match for i = 0, fallbacks[q] = number of parent() calls (may be NULL).  Needs the LCP array.
+ * The dense calls take no maximum match length (gcsa2_match_breaks_bounded_device below): after a cut the search goes on from
+ * the parent of the capped range, and one statistic per position does not follow from the capped records. */
 int gcsa2_match_stats_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets,
                             uint64_t n_queries, uint16_t* ms, uint64_t* ranges, uint64_t* fallbacks);
 int gcsa2_match_stats_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets,
@@ -443,6 +445,42 @@ int gcsa2_match_breaks_device(const gcsa2_index* index, const uint8_t* d_pattern
 int gcsa2_match_breaks_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
                              uint64_t min_length, uint64_t* break_offsets, gcsa2_break* breaks, uint64_t capacity,
                              uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks);
+/* The break points with a MAXIMUM MATCH LENGTH.  The index answers for patterns up to its order: "the pattern may be longer
+ * than the order of the index, but this may result in false positives" (the reference, include/gcsa/gcsa.h:91, and its
+ * README), so a record longer than gcsa2_order() may describe a path the graph does not have.  A mapper bounds its matches:
+ * one that has reached max_length characters is cut as if the next character had failed, and the search goes on from
+ * parent().  This is not a filter of the unbounded records -- after a cut the walk continues from the parent of the CAPPED
+ * range, and the records that follow differ in position, length and range.  The definition is this walk over
+ * GCSA::LF(range, comp) (gcsa.h:155-162) and LCPArray::parent(range) (src/lcp.cpp:276-301), per pattern P, right to left,
+ * n = gcsa2_size():
+ *
+ *   i = |P|; r = (0, n - 1); depth = 0; last = none; parents = 0
+ *   while i > 0:
+ *     if not (max_length > 0 and depth >= max_length):
+ *       r2 = LF(r, char2comp[P[i - 1]])
+ *       if r2 is not empty: r = r2; depth += 1; i -= 1; continue
+ *     if r == (0, n - 1):                                   (the root: reached through a failed LF only)
+ *       depth = 0; i -= 1
+ *       if i + 1 < |P| and last != i + 1: record {i + 1, 0, 0, n - 1}; last = i + 1
+ *       continue
+ *     if last != i: record {i, depth, r.sp, r.ep}; last = i
+ *     p = parent(r); r = (p.sp, p.ep); depth = p.lcp; parents += 1
+ *   if |P| > 0 and last != 0: record {0, depth, r.sp, r.ep}
+ *
+ * The records of length >= min_length are kept, in this order (descending position); d_fallbacks[q] = parents, the parent()
+ * calls forced by the cap included; d_ranges[2q..] = r at the end.  Every record has length <= max_length and (sp, ep) =
+ * find(P[position, position + length)).  max_length == 0: no cap -- the walk is then the contract of gcsa2_match_breaks_device,
+ * and the results are the same bit for bit; a max_length of 2^32 or more can never be reached and means the same.  A mapper
+ * passes gcsa2_order().  max_length != 0 && min_length > max_length: GCSA2_ERR_INVALID_ARGUMENT, nothing is written.
+ * Everything else -- buffers, capacity, *total_breaks, variant, pieces of the host form -- as the unbounded calls, which are
+ * these with max_length = 0. */
+int gcsa2_match_breaks_bounded_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_queries,
+                                      uint64_t total_pattern_bytes, int variant, uint64_t min_length, uint64_t max_length,
+                                      uint64_t* d_break_offsets, gcsa2_break* d_breaks, uint64_t capacity, uint64_t* total_breaks,
+                                      uint64_t* d_ranges, uint64_t* d_fallbacks, void* stream);
+int gcsa2_match_breaks_bounded_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
+                                     uint64_t min_length, uint64_t max_length, uint64_t* break_offsets, gcsa2_break* breaks,
+                                     uint64_t capacity, uint64_t* total_breaks, uint64_t* ranges, uint64_t* fallbacks);
 /* MEM hits: the break records of gcsa2_match_breaks_device with count() and their positions, a MEM finder's seeds in one
  * call.  MEMs of pattern q: d_mems[d_mem_offsets[q] .. d_mem_offsets[q + 1]), exactly the records gcsa2_match_breaks_device
  * returns for min_length (min_length >= 1, GCSA2_ERR_INVALID_ARGUMENT otherwise), in the same order, each with
@@ -472,6 +510,19 @@ int gcsa2_mem_hits_batch(const gcsa2_index* index, const uint8_t* patterns, cons
                          uint64_t min_length, uint64_t hit_max, int over,
                          uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
                          uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* MEM hits with a maximum match length: the MEMs are exactly the records gcsa2_match_breaks_bounded_device returns for
+ * (min_length, max_length) -- the walk stated there --, counts and hits by the rules of gcsa2_mem_hits_device.  max_length == 0
+ * (or >= 2^32): no cap, the unbounded calls; max_length != 0 && min_length > max_length: GCSA2_ERR_INVALID_ARGUMENT, nothing is
+ * written.  The pieces of the host form all run under the same max_length.  Sub-MEM reseeding (below) needs no cap of its own:
+ * its matches lie inside the MEMs it is given. */
+int gcsa2_mem_hits_bounded_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_queries,
+                                  uint64_t total_pattern_bytes, uint64_t min_length, uint64_t max_length, uint64_t hit_max, int over,
+                                  uint64_t* d_mem_offsets, gcsa2_mem* d_mems, uint64_t mem_capacity, uint64_t* total_mems,
+                                  uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+int gcsa2_mem_hits_bounded_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_queries,
+                                 uint64_t min_length, uint64_t max_length, uint64_t hit_max, int over,
+                                 uint64_t* mem_offsets, gcsa2_mem* mems, uint64_t mem_capacity, uint64_t* total_mems,
+                                 uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* Sub-MEM reseeding: inside every MEM of at least reseed_length bases, the shorter matches that occur MORE OFTEN than the MEM
  * (vg's GCSA mapper reseeds such MEMs: a long, nearly unique match may cross a SNP or come from a paralog), with count() and
  * hits.  Input: the patterns and a MEM CSR as gcsa2_mem_hits_device returns it -- MEMs of pattern q are
