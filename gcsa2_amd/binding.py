@@ -41,6 +41,7 @@ EXPORTS = [
     "gcsa2_comm_unique_id", "gcsa2_comm_create", "gcsa2_comm_create_custom", "gcsa2_comm_destroy", "gcsa2_comm_rank", "gcsa2_comm_world", "gcsa2_comm_rccl_ranks", "gcsa2_comm_gather",
     "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch",
     "gcsa2_match_breaks_bounded_device", "gcsa2_match_breaks_bounded_batch", "gcsa2_mem_hits_bounded_device", "gcsa2_mem_hits_bounded_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
+    "gcsa2_extend_device", "gcsa2_extend_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -158,6 +159,8 @@ def load_library():
     L.gcsa2_mem_hits_bounded_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_sub_mem_hits_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_sub_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64p, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_extend_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
+    L.gcsa2_extend_batch.argtypes = [vp, u8p, u64p, u64, vp, u64, vp]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
     L.gcsa2_group_destroy.argtypes = [vp]
     L.gcsa2_group_destroy.restype = None
@@ -446,6 +449,23 @@ class GCSA:
         out = np.zeros_like(ranges)
         _check(self._L.gcsa2_lf_batch(self._h, _p64(ranges), _p8(comps), ranges.shape[0], _p64(out)))
         return out
+
+    def extend_batch(self, patterns, offsets, states):
+        """The backward search continued from caller ranges (gcsa2_extend_batch): `states` is an (n, 5) uint64 array of
+        (pattern, begin, end, sp, ep) -- continue from (sp, ep) over P[begin, end) of pattern `pattern`, last character first.
+        Returns (n, 5) uint64 rows (matched, sp, ep, last_sp, last_ep): the steps that left a non-empty range, the range the
+        reference's loop ends with, and the last non-empty range.  An invalid state has matched = 2^64 - 1 and its start range."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        states = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 5)
+        out = np.zeros_like(states)
+        _check(self._L.gcsa2_extend_batch(self._h, _p8(patterns), _p64(offsets), max(offsets.shape[0], 1) - 1, states.ctypes.data,
+                                          states.shape[0], out.ctypes.data))
+        return out
+
+    def extend_device(self, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out, stream=0):
+        """gcsa2_extend_device on caller-owned device buffers: enqueues on `stream` and returns."""
+        _check(self._L.gcsa2_extend_device(self._h, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out, stream))
 
     def lf_node_batch(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)

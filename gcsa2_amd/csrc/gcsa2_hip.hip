@@ -43,6 +43,7 @@ using namespace g2;
 
 #include "kernels_common.hpp"
 #include "kernels_find.hpp"
+#include "kernels_extend.hpp"
 #include "kernels_locate.hpp"
 #include "kernels_locate_max.hpp"
 #include "kernels_mem.hpp"
@@ -1400,6 +1401,24 @@ int gcsa2_lf_device(const gcsa2_index* ix, const uint64_t* d_in, const uint8_t* 
   return GCSA2_OK;
 }
 
+// extend: the backward search continued from caller ranges (kernels_extend.hpp); enqueue only, invalid states are marked by the kernel
+int gcsa2_extend_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                        const gcsa2_search_state* d_states, uint64_t n_states, gcsa2_extension* d_out, void* stream)
+{
+  CHECK_INDEX(ix);
+  if(n_states == 0) { return GCSA2_OK; }
+  if(d_states == nullptr || d_out == nullptr || (n_patterns > 0 && d_offsets == nullptr)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  if(n_states >= (u64(1) << 31) * TPB2) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "extend: 2^38 or more states in one launch; split the batch"); }
+  DeviceGuard guard(ix->device);          // the launch goes to the index's device whatever the caller's current one is
+  static_assert(sizeof(gcsa2_search_state) == 40 && sizeof(gcsa2_extension) == 40, "five u64 each");
+  const dim3 grid(unsigned((n_states + TPB2 - 1) / TPB2));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(ix->img.flp != nullptr) { hipLaunchKernelGGL(k_extend<true>, grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out); }
+  else { hipLaunchKernelGGL(k_extend<false>, grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out); }
+  LAUNCH_CHECK("k_extend");
+  return GCSA2_OK;
+}
+
 int gcsa2_count_device(const gcsa2_index* ix, const uint64_t* d_ranges, uint64_t nq, uint64_t* d_counts, void* stream)
 {
   CHECK_INDEX(ix);
@@ -2247,6 +2266,31 @@ int gcsa2_lf_batch(const gcsa2_index* ix, const uint64_t* in, const uint8_t* com
   int rc = gcsa2_lf_device(ix, d_in, d_c, nq, d_out, lease.stream());
   if(rc != GCSA2_OK) { return rc; }
   HIP_TRY(lease.down(out, d_out, 2 * nq * sizeof(u64)));
+  HIP_TRY(lease.finish());
+  return GCSA2_OK;
+}
+
+// The host form of extend, in one piece: patterns, offsets and states copied in, one launch, the results copied out.
+int gcsa2_extend_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                       const gcsa2_search_state* states, uint64_t n_states, gcsa2_extension* out)
+{
+  CHECK_INDEX(ix);
+  if(n_states == 0) { return GCSA2_OK; }
+  if(states == nullptr || out == nullptr || (n_patterns > 0 && offsets == nullptr)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  if(n_patterns > 0 && (offsets[0] != 0 || !offsets_ok(offsets, n_patterns))) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  const u64 total = (n_patterns > 0 ? offsets[n_patterns] : 0);
+  if(patterns == nullptr && total > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  DeviceGuard guard(ix->device);
+  Lease lease(ix);
+  HIP_TRY(lease.begin(Lease::need(total + 16) + Lease::need((n_patterns + 1) * 8) + 2 * Lease::need(n_states * 40), true));
+  u8* d_pat = lease.dev<u8>(total + 16); u64* d_off = lease.dev<u64>(n_patterns + 1);
+  gcsa2_search_state* d_states = lease.dev<gcsa2_search_state>(n_states); gcsa2_extension* d_out = lease.dev<gcsa2_extension>(n_states);
+  HIP_TRY(lease.up(d_pat, patterns, total));
+  if(n_patterns > 0) { HIP_TRY(lease.up(d_off, offsets, (n_patterns + 1) * sizeof(u64))); }
+  HIP_TRY(lease.up(d_states, states, n_states * sizeof(gcsa2_search_state)));
+  int rc = gcsa2_extend_device(ix, d_pat, d_off, n_patterns, d_states, n_states, d_out, lease.stream());
+  if(rc != GCSA2_OK) { return rc; }
+  HIP_TRY(lease.down(out, d_out, n_states * sizeof(gcsa2_extension)));
   HIP_TRY(lease.finish());
   return GCSA2_OK;
 }

@@ -120,6 +120,20 @@ public:
     return result;
   }
 
+  // Batched extend (gcsa2_extend_batch): state s continues the loop of find() from the range (sp, ep) over
+  // P[begin, end) of pattern s.pattern -- what a caller's loop of LF(range, comp) from a stored range does, for many
+  // states and without copying substrings out.  An invalid state comes back with matched = GCSA2_UNKNOWN.
+  std::vector<gcsa2_extension> extend_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets,
+                                            const std::vector<gcsa2_search_state>& states) const
+  {
+    size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::vector<gcsa2_extension> result(states.size());
+    std::uint8_t dummy = 0;
+    check(gcsa2_extend_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.data(), np, states.data(), states.size(),
+                             result.data()), "GCSA::extend_batch()");
+    return result;
+  }
+
   // Batched find of k-mers handed over as 2-bit codes (gcsa2_find_batch_packed: `length` characters each, last character
   // first, comp - 1 in two bits, ceil(length / 32) words per pattern): 8 instead of 40 bytes per 32-mer over the link.
   std::vector<range_type> find_packed_batch(const std::vector<std::uint64_t>& codes, size_type length) const

@@ -251,6 +251,48 @@ int gcsa2_char_range(const gcsa2_index* index, uint8_t comp, uint64_t* sp, uint6
 int gcsa2_lf_all_batch(const gcsa2_index* index, const uint64_t* ranges_in, uint64_t n_queries,
                        int all, uint64_t* ranges_out);
 
+/* ---- extend: the loop of GCSA::find (gcsa.h:96-110) continued from caller ranges ------------------------------------------
+ * The reference's low-level interface (LF(range, comp), gcsa.h:133-162) is public so that a caller can keep a SEARCH STATE --
+ * a range plus a cursor into a read -- and carry it on later: a branch of a fan-out over the bases at a low-quality position,
+ * a seed resumed from a stored range, find() of a substring of a read.  One call continues n_states such searches, each over
+ * a substring of one pattern of a shared pattern set, in one launch.  (d_patterns, d_offsets) is the pattern CSR of
+ * gcsa2_find_device: n_patterns + 1 offsets, alignment and padding as under "Conventions"; many states may name one pattern.
+ *
+ * For one state s, with P = pattern s.pattern, the result is DEFINED by this walk:
+ *
+ *   r = (s.sp, s.ep); last = r; matched = 0; i = s.end
+ *   while i > s.begin and not empty(r):            (Range::empty, utils.h:93-96)
+ *     i -= 1; r = LF(r, char2comp[P[i]])           (gcsa.h:155-162)
+ *     if not empty(r): matched += 1; last = r
+ *   out = { matched, r.sp, r.ep, last.sp, last.ep }
+ *
+ * What follows from it:
+ *   - (sp, ep) is exactly what the reference's loop `while(!empty(range) && end != begin) range = LF(range, *--end)` leaves:
+ *     when a step empties the range, that step's edge-space integers (gcsa.h:160), as find() returns them.
+ *   - (last_sp, last_ep) is the range of the longest matched suffix P[end - matched, end) extended from the start range; it
+ *     equals (sp, ep) when no step emptied.
+ *   - An empty start range, begin == end or an index of size 0: the start range in both places, matched = 0.
+ *   - A state that starts at (0, size() - 1) gives find(P[begin, end)) whenever that is non-empty; both are empty otherwise
+ *     (find() starts from charRange of the last character, whose empty form differs from the edge-space pair of an LF step).
+ *   - find(P) == extend(find(P[c:]), P[:c]) for every cut c < |P|, empty results included, bit for bit (c = |P| is the
+ *     start at the root of the line above).
+ *   - An INVALID state -- pattern >= n_patterns, begin > end, or end beyond the pattern's length -- is not searched and no
+ *     pattern byte is read for it: out = { GCSA2_UNKNOWN, s.sp, s.ep, s.sp, s.ep }.  So the device form needs no read-back
+ *     to refuse a state, and a bad cursor cannot fault the GPU.
+ *   - The ranges themselves are not validated, like the rest of the low-level interface.
+ *
+ * gcsa2_extend_device only enqueues on `stream`.  n_states == 0 is GCSA2_OK; a NULL index is GCSA2_ERR_INVALID_ARGUMENT before
+ * any device is touched.  gcsa2_extend_batch takes host pointers, requires offsets[0] == 0, runs in one piece (patterns,
+ * offsets, states and results must fit in device memory together) and is complete on return.  Where the image has pair
+ * blocks (gcsa2_pair_block_bytes) two characters cost one memory request per endpoint whenever both steps stay non-empty;
+ * anything else is stepped singly, so every field is the walk's. */
+typedef struct gcsa2_search_state { uint64_t pattern, begin, end, sp, ep; } gcsa2_search_state;
+typedef struct gcsa2_extension    { uint64_t matched, sp, ep, last_sp, last_ep; } gcsa2_extension;
+int gcsa2_extend_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                        const gcsa2_search_state* d_states, uint64_t n_states, gcsa2_extension* d_out, void* stream);
+int gcsa2_extend_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                       const gcsa2_search_state* states, uint64_t n_states, gcsa2_extension* out);
+
 /* ---- count: GCSA::count(range) (src/gcsa.cpp:802-809) -------------------------------------- */
 int gcsa2_count_batch(const gcsa2_index* index, const uint64_t* ranges, uint64_t n_queries,
                       uint64_t* counts);
