@@ -164,6 +164,13 @@ inline unsigned grid_for(u64 n) { return unsigned((n + TPB - 1) / TPB); }
 // what a memory budget (GCSA2_MEMORY_BUDGET_MB, read at create time) leaves for the next optional table
 inline u64 budget_left(const gcsa2_index* ix) { return ix->tune.budget_bytes > ix->bytes ? ix->tune.budget_bytes - ix->bytes : 0; }
 
+// The jump table of a find-only image is built without being asked for (gcsa2_index_create).
+constexpr bool JUMP_DEFAULT_FIND_ONLY = true;
+// Free-memory test of the jump table, the largest optional table (16 bytes per path node; the others take a fraction
+// of what is free): `bytes` more must leave a sixteenth of the device's memory free for the caller's batches and the
+// handle's scratch pool -- 18 GB of a 288 GB device, where the 91.6 GB table of a 5.73 G-node index goes on top of a 175 GB image.
+inline bool jump_table_fits(u64 bytes, u64 free_bytes, u64 total_bytes) { return bytes <= free_bytes && free_bytes - bytes >= total_bytes / 16; }
+
 inline void launch_walk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, const u64* node_off, const u64* raw_off,
                         u64 total_nodes, u64* values, u64* owners, hipStream_t stream);
 
@@ -1076,29 +1083,41 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       (void)make_locate_table(ix);
     }
   }
-  // memoised unary LF chains for find(): 16 bytes per path node, opt-in (GCSA2_JUMP_TABLE=1).  Built by
-  // doubling (1 -> 2 -> 4 -> 8 steps) with a second buffer that is released afterwards.
+  // memoised unary LF chains for find(): 16 bytes per path node.  An image WITH samples has it only on request
+  // (GCSA2_JUMP_TABLE=1; round 2: the table costs more than the locate table and such an image serves locate() too).  A
+  // find-only image -- created without samples, so it has no locate table and find() is all it serves -- gets it by
+  // default (JUMP_DEFAULT_FIND_ONLY), in the locate table's place: last under a memory budget, and only where it leaves
+  // a sixteenth of the device free (jump_table_fits); GCSA2_JUMP_TABLE=0 switches it off.  Two builders with identical output: doubling
+  // (1 -> 2 -> 4 -> 8 steps) through a second buffer that is released afterwards where both buffers pass the
+  // free-memory test, otherwise one pass of chain walks into the table itself (k_jump_walk); GCSA2_JUMP_BUILD=double|walk
+  // forces one of them (tests).  A table that cannot be had is left out without an error.
   ix->img.jump_tab = nullptr;
   {
     const char* env = std::getenv("GCSA2_JUMP_TABLE");
+    const char* how = std::getenv("GCSA2_JUMP_BUILD");
     size_t free_bytes = 0, total_bytes = 0;
     const u64 n = ix->img.n, bytes = n * sizeof(ulonglong2);
-    if(env != nullptr && std::atoi(env) != 0 && n > 0 && n <= JUMP_NODE_MASK && ix->img.sigma >= 5 &&
+    const bool wanted = (env != nullptr && *env != 0 ? std::atoi(env) != 0 : JUMP_DEFAULT_FIND_ONLY && !ix->img.has_samples);
+    if(wanted && n > 0 && n <= JUMP_NODE_MASK && ix->img.sigma >= 5 &&
        (ix->tune.budget_bytes == 0 || bytes <= budget_left(ix)) &&
-       hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess && 2 * bytes <= free_bytes / 2)
+       hipMemGetInfo(&free_bytes, &total_bytes) == hipSuccess && jump_table_fits(bytes, free_bytes, total_bytes))
     {
+      bool doubling = jump_table_fits(2 * bytes, free_bytes, total_bytes);
+      if(how != nullptr && std::strcmp(how, "walk") == 0) { doubling = false; }
+      if(how != nullptr && std::strcmp(how, "double") == 0) { doubling = true; }        // a failed allocation still ends without a table
       void* other = nullptr;
       hipError_t e = hipMalloc(&ix->d_jump, bytes);
-      if(e == hipSuccess) { e = hipMalloc(&other, bytes); }
+      if(e == hipSuccess && doubling) { e = hipMalloc(&other, bytes); }
       ulonglong2 *a = static_cast<ulonglong2*>(ix->d_jump), *b = static_cast<ulonglong2*>(other);
       const u64 slice = u64(1) << 30;
       for(u64 first = 0; first < n && e == hipSuccess; first += slice)
       {
         u64 count = (n - first < slice ? n - first : slice);
-        hipLaunchKernelGGL(k_jump_init, dim3(grid_for(count)), dim3(TPB), 0, nullptr, ix->img, first, a);
+        if(doubling) { hipLaunchKernelGGL(k_jump_init, dim3(grid_for(count)), dim3(TPB), 0, nullptr, ix->img, first, a); }
+        else { hipLaunchKernelGGL(k_jump_walk, dim3(grid_for(count)), dim3(TPB), 0, nullptr, ix->img, first, a); }
         e = hipGetLastError();
       }
-      for(u32 have = 1; have < JUMP_MAX && e == hipSuccess; have *= 2)
+      for(u32 have = 1; doubling && have < JUMP_MAX && e == hipSuccess; have *= 2)
       {
         for(u64 first = 0; first < n && e == hipSuccess; first += slice)
         {
@@ -1112,7 +1131,8 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       // three doubling rounds: the result is in the buffer that was `other` at the start
       if(e == hipSuccess)
       {
-        (void)hipFree(b); ix->d_jump = a;
+        if(b) { (void)hipFree(b); }
+        ix->d_jump = a;
         ix->img.jump_tab = a; ix->bytes += bytes;
       }
       else

@@ -649,6 +649,9 @@ __global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : FIND_WAVES) void k_find
         {
           sp = ep = (take == len ? jt_end(entry) : (take == 4 ? jt_after4(entry) : jt_after2(entry)));
           i -= take; win_used += take; done = (i == 0);
+          // A whole chain shorter than JUMP_MAX ended because the node it reaches is not forced: its entry is empty, so
+          // step from it instead of looking it up.
+          tried = (take == len && len < JUMP_MAX);
           if(STATS) { steps += take; }
         }
         else
@@ -871,6 +874,39 @@ __global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restric
     e = jt_make(end, after4, after2, labels & 0xFFFF, len);
   }
   out[v] = e;
+}
+
+// The same table without a second buffer: every node walks its own forced chain (at most JUMP_MAX steps) and writes its
+// final entry.  What the doubling leaves in an entry is a function of the chain alone -- len = the number of consecutive
+// forced nodes from v on, capped at 8; the node after len steps; the node after 4 steps when len >= 4 and after 2 steps
+// when len >= 2, zero otherwise; the labels of the len steps; the all-zero entry when v itself is not forced -- so the
+// two builders write identical bits.  Costs up to 8 dependent LF steps per node against the doubling's 1 + 3 passes; it
+// is what an index takes whose table fits the device but not twice.
+__global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulonglong2* __restrict__ table)
+{
+  __shared__ Tables t;
+  stage_tables(img, t);
+  u64 v = first + u64(blockIdx.x) * TPB + threadIdx.x;
+  if(v >= img.n) { return; }
+  u64 cur = v, after2 = 0, after4 = 0;
+  u32 labels = 0, len = 0;
+  while(len < JUMP_MAX && cur < img.n)
+  {
+    u32 incoming = 0, comp = 0;
+    u64 rank = 0;
+    for(u32 c = 0; c < u32(img.sigma); c++)
+    {
+      u64 r;
+      if(bv_get_rank(bwt_of(img, c), cur, r)) { incoming++; comp = c; rank = r; }
+    }
+    if(incoming != 1 || comp - 1 >= 4) { break; }
+    cur = bv_rank(img.edges, clampu(t.C[comp] + rank, img.e));         // lf_node() of a node whose only label is comp
+    labels |= (comp - 1) << (2 * len);
+    len++;
+    if(len == 2) { after2 = cur; }
+    if(len == 4) { after4 = cur; }
+  }
+  table[v] = (len > 0 ? jt_make(cur, after4, after2, labels, len) : make_ulonglong2(0, 0));
 }
 
 // LF_fast (all = 0, comps 1..fast_chars) / LF_all (all = 1, comps 1..sigma-2); src/gcsa.cpp:742-798

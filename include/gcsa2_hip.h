@@ -217,12 +217,19 @@ uint64_t gcsa2_kmer_table_k(const gcsa2_index* index);
  * one 8-byte entry per path node instead of walking.  Needs samples; skipped when it would take
  * more than a third of the free device memory or when GCSA2_LOCATE_TABLE=0. */
 uint64_t gcsa2_locate_table_bytes(const gcsa2_index* index);
-/* Bytes of the jump table (0 = none; built when GCSA2_JUMP_TABLE=1): for every path node the chain of
+/* Bytes of the jump table (0 = none): for every path node the chain of
  * up to 8 LF steps that is forced because each node on it has a single incoming label (a fast
  * character), with the node it ends in.  find() on a range of one path node whose next pattern
  * characters spell that chain moves there with one 16-byte lookup instead of one block fetch per
  * character; any other case steps as usual, so results (including the edge-space empty ranges of
- * include/gcsa/gcsa.h:160) are unchanged.  16 bytes per path node. */
+ * include/gcsa/gcsa.h:160) are unchanged.  16 bytes per path node.
+ * GCSA2_JUMP_TABLE (read at create time): unset -- built for a find-only image (one created without samples: no
+ * locate(), no locate table; the jump table takes that table's place, last under GCSA2_MEMORY_BUDGET_MB) and not for an
+ * image with samples; 1 -- attempted on any image; 0 -- never.  In every case only where the table leaves a sixteenth of
+ * the device's memory free; an image that cannot have it is created without it, with no error.
+ * GCSA2_JUMP_BUILD=double|walk (tests) forces one of the two builders, whose tables are identical: doubling through a
+ * second buffer of the table's size (the default where both buffers pass the free-memory test), or one pass of chain
+ * walks that needs no second buffer. */
 uint64_t gcsa2_jump_table_bytes(const gcsa2_index* index);
 /* Bytes of the two-characters-per-step blocks (0 = none).  For every ordered pair of fast characters the
  * composition of two LF steps (gcsa.h:155-162 applied twice) is stored as one rank structure of 128-byte
