@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GCSA2_HIP_LIB") or os.path.join(_HERE, "lib", "libgcsa2_hip.so")   # override: A/B runs of two builds
 
 STATUS_BUFFER_TOO_SMALL = -6
+KMER_COUNTS = 1     # GCSA2_KMER_COUNTS
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -41,7 +42,7 @@ EXPORTS = [
     "gcsa2_comm_unique_id", "gcsa2_comm_create", "gcsa2_comm_create_custom", "gcsa2_comm_destroy", "gcsa2_comm_rank", "gcsa2_comm_world", "gcsa2_comm_rccl_ranks", "gcsa2_comm_gather",
     "gcsa2_pack_ranges32_device", "gcsa2_unpack_ranges32_device", "gcsa2_pack_ranges40_device", "gcsa2_unpack_ranges40_device", "gcsa2_wire48_bytes", "gcsa2_mailbox_stats", "gcsa2_pack_ranges48_device", "gcsa2_unpack_ranges48_device", "gcsa2_count_kmers", "gcsa2_compare_kmers", "gcsa2_compare_kmers_records", "gcsa2_match_stats_batch", "gcsa2_match_stats_device", "gcsa2_match_stats_device_variant", "gcsa2_match_stats_device_sized", "gcsa2_match_stats_profile_device", "gcsa2_match_breaks_device", "gcsa2_match_breaks_batch", "gcsa2_mem_hits_device", "gcsa2_mem_hits_batch",
     "gcsa2_match_breaks_bounded_device", "gcsa2_match_breaks_bounded_batch", "gcsa2_mem_hits_bounded_device", "gcsa2_mem_hits_bounded_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
-    "gcsa2_extend_device", "gcsa2_extend_batch",
+    "gcsa2_extend_device", "gcsa2_extend_batch", "gcsa2_kmer_windows_device", "gcsa2_kmer_windows_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -161,6 +162,8 @@ def load_library():
     L.gcsa2_sub_mem_hits_batch.argtypes = [vp, u8p, u64p, u64, u64p, vp, u64, u64, u64, u64, i32, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_extend_device.argtypes = [vp, vp, vp, u64, vp, u64, vp, vp]
     L.gcsa2_extend_batch.argtypes = [vp, u8p, u64p, u64, vp, u64, vp]
+    L.gcsa2_kmer_windows_device.argtypes = [vp, vp, vp, u64, u64, u64, C.c_int, vp, vp, vp, vp, u64, u64p, vp]
+    L.gcsa2_kmer_windows_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, C.c_int, vp, vp, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
     L.gcsa2_group_destroy.argtypes = [vp]
     L.gcsa2_group_destroy.restype = None
@@ -466,6 +469,51 @@ class GCSA:
     def extend_device(self, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out, stream=0):
         """gcsa2_extend_device on caller-owned device buffers: enqueues on `stream` and returns."""
         _check(self._L.gcsa2_extend_device(self._h, d_patterns, d_offsets, n_patterns, d_states, n_states, d_out, stream))
+
+    def kmer_windows_batch(self, patterns, offsets, k, stride=1, counts=False, ranges=True, profiles=True, occurrences=False):
+        """find() (and count()) of every window P_q[j stride, j stride + k) of every read of a batch in host memory
+        (gcsa2_kmer_windows_batch).  Returns (window_offsets, profiles, ranges, counts): window_offsets (reads + 1) is the
+        exclusive prefix sum of the windows per read, profiles (reads, 4) holds (windows, found, nodes, occurrences) per read,
+        ranges (windows, 2) is find() of each window and counts (windows) its count(); None for what was not asked.
+        `counts` also fills profiles' occurrences; `occurrences=True` does that without the counts array.  Either needs the
+        counters."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        k, stride = int(k), int(stride)
+        flags = KMER_COUNTS if (counts or occurrences) else 0
+        total = 0
+        if n > 0 and k > 0 and stride > 0 and (ranges or counts):          # the sizes of the per-window arrays (the call checks the rest)
+            lens = np.diff(offsets.astype(np.int64))
+            total = int(np.where(lens >= k, (lens - k) // stride + 1, 0).sum())
+        woff = np.zeros(n + 1, dtype=np.uint64)
+        prof = np.zeros((n, 4), dtype=np.uint64) if profiles else None
+        rng = np.zeros((total, 2), dtype=np.uint64) if ranges else None
+        cnt = np.zeros(total, dtype=np.uint64) if counts else None
+        needed = C.c_uint64()
+        rc = self._L.gcsa2_kmer_windows_batch(self._h, _p8(patterns), _p64(offsets), n, k, stride, flags, woff.ctypes.data,
+                                              None if prof is None else prof.ctypes.data, None if rng is None else rng.ctypes.data,
+                                              None if cnt is None else cnt.ctypes.data, total, C.byref(needed))
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = needed.value
+            raise err
+        return woff, prof, rng, cnt
+
+    def kmer_windows_device(self, d_patterns, d_offsets, n_patterns, k, stride, flags, d_window_offsets, d_profiles, d_ranges, d_counts,
+                            capacity, stream=0):
+        """gcsa2_kmer_windows_device on caller-owned device buffers (raw pointers; 0 / None for an output that is not wanted):
+        d_window_offsets n_patterns + 1 u64, d_profiles n_patterns records of four u64, d_ranges / d_counts `capacity` windows.
+        Complete on return.  Returns the number of windows; raises Gcsa2Error with `.needed` = that number otherwise
+        (BUFFER_TOO_SMALL: more than `capacity`)."""
+        needed = C.c_uint64()
+        rc = self._L.gcsa2_kmer_windows_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(flags), d_window_offsets or None,
+                                               d_profiles or None, d_ranges or None, d_counts or None, int(capacity), C.byref(needed), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = needed.value
+            raise err
+        return needed.value
 
     def lf_node_batch(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)

@@ -15,6 +15,8 @@
 //                                                                        src/gcsa.cpp:827-842, 880-896, utils.h:350-357
 //                       k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
+//   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
+//                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
 #include "sdsl_reader.hpp"
@@ -47,6 +49,7 @@ using namespace g2;
 #include "kernels_locate.hpp"
 #include "kernels_locate_max.hpp"
 #include "kernels_mem.hpp"
+#include "kernels_windows.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_submem.hpp"
 #include "kernels_mailbox.hpp"
@@ -5076,6 +5079,173 @@ int gcsa2_sub_mem_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   if(h > 0) { HIP_TRY(hipMemcpy(hits, d_hits.p, h * sizeof(u64), hipMemcpyDeviceToHost)); }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_sub_mem_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== k-mer windows: find() / count() of every window of every read, per-read profiles (kernels_windows.hpp) ================
+namespace {
+
+// what both forms refuse before any device is touched, then the one component the call may need
+int kmer_windows_checks(const gcsa2_index* ix, u64 k, u64 stride, int flags, const void* counts, const u64* total_windows)
+{
+  CHECK_INDEX(ix);
+  if(total_windows == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_windows: k must be at least 1"); }
+  if(stride == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_windows: stride must be at least 1"); }
+  if((flags & ~GCSA2_KMER_COUNTS) != 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_windows: unknown flag"); }
+  if(counts != nullptr && (flags & GCSA2_KMER_COUNTS) == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_windows: a counts buffer needs GCSA2_KMER_COUNTS"); }
+  if((flags & GCSA2_KMER_COUNTS) != 0 && !ix->img.has_counters) { return fail(GCSA2_ERR_MISSING_COMPONENT, "index was created without counters"); }
+  return GCSA2_OK;
+}
+
+// gcsa2_kmer_windows_device after its argument checks (n_patterns > 0).  One host round trip: the number of windows.
+int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, int flags,
+                      u64* d_window_offsets, gcsa2_kmer_profile* d_profiles, u64* d_ranges, u64* d_counts, u64 capacity, u64* total_windows,
+                      hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *sizes = nullptr, *woff = d_window_offsets;
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  if(woff == nullptr) { HIP_TRY(scratch.get(woff, n_patterns + 1)); }
+  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
+  LAUNCH_CHECK("k_window_counts");
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  u64 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  *total_windows = total;
+  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_windows: 2^32 or more windows in one call; split the batch"); }
+  if((d_ranges != nullptr || d_counts != nullptr) && total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "window buffer too small"); }
+  if(d_profiles == nullptr && d_ranges == nullptr && d_counts == nullptr) { return GCSA2_OK; }
+  scratch.settled = false;
+  static_assert(sizeof(gcsa2_kmer_profile) == 32, "four u64");
+  if(d_profiles != nullptr) { HIP_TRY(hipMemsetAsync(d_profiles, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
+  if(total > 0)
+  {
+    const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
+    const bool pair = ix->img.flp != nullptr, count = (flags & GCSA2_KMER_COUNTS) != 0 && (d_counts != nullptr || d_profiles != nullptr);
+    // the reads of every wavefront's first window: the bracket in which a lane looks for its own read
+    const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+    u64* owners = nullptr;
+    HIP_TRY(scratch.get(owners, spans + 1));
+    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
+    LAUNCH_CHECK("k_block_owners");
+#define KMER_WINDOWS_LAUNCH(P, C) hipLaunchKernelGGL((k_kmer_windows<P, C>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, \
+                                                     woff, owners, total, d_ranges, d_counts, d_profiles)
+    if(pair) { if(count) { KMER_WINDOWS_LAUNCH(true, true); } else { KMER_WINDOWS_LAUNCH(true, false); } }
+    else { if(count) { KMER_WINDOWS_LAUNCH(false, true); } else { KMER_WINDOWS_LAUNCH(false, false); } }
+#undef KMER_WINDOWS_LAUNCH
+    LAUNCH_CHECK("k_kmer_windows");
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_windows_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                              uint64_t stride, int flags, uint64_t* d_window_offsets, gcsa2_kmer_profile* d_profiles, uint64_t* d_ranges,
+                              uint64_t* d_counts, uint64_t capacity, uint64_t* total_windows, void* stream)
+{
+  int rc = kmer_windows_checks(ix, k, stride, flags, d_counts, total_windows);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_windows = 0;
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_windows: 2^32 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    if(d_window_offsets != nullptr)
+    {
+      HIP_TRY(hipMemsetAsync(d_window_offsets, 0, sizeof(u64), st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    return GCSA2_OK;
+  }
+  return kmer_windows_core(ix, d_patterns, d_offsets, n_patterns, k, stride, flags, d_window_offsets, d_profiles, d_ranges, d_counts, capacity,
+                           total_windows, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_windows_device: ") + e.what()); }
+}
+
+// The host form.  The window offsets are a function of the pattern offsets alone, so they -- and the total, and the refusal of
+// a short buffer -- are worked out here before any device work.  A batch of two pieces' worth of pattern bytes or more is cut
+// into pieces of reads (tune.ms_piece_bytes, cut_pieces) that tune.ms_threads host threads carry: reads and their rebased
+// offsets in, gcsa2_kmer_windows_device with the window offsets left in scratch, then the piece's profiles / ranges / counts
+// out to their places in the caller's arrays, which the host-side offsets name.  With profiles as the only output that is
+// the reads in and 32 bytes per read out.
+int gcsa2_kmer_windows_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                             uint64_t stride, int flags, uint64_t* window_offsets, gcsa2_kmer_profile* profiles, uint64_t* ranges,
+                             uint64_t* counts, uint64_t capacity, uint64_t* total_windows)
+{
+  int rc = kmer_windows_checks(ix, k, stride, flags, counts, total_windows);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_windows = 0;
+  if(n_patterns == 0) { if(window_offsets != nullptr) { window_offsets[0] = 0; } return GCSA2_OK; }
+  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  std::vector<u64> woff(n_patterns + 1);
+  u64 total = 0;
+  for(u64 q = 0; q < n_patterns; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    woff[q] = total;
+    if(len >= k) { total += (len - k) / stride + 1; }
+  }
+  woff[n_patterns] = total;
+  *total_windows = total;
+  if((ranges != nullptr || counts != nullptr) && total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "window buffer too small"); }
+  if(window_offsets != nullptr) { std::memcpy(window_offsets, woff.data(), (n_patterns + 1) * sizeof(u64)); }
+  if(profiles == nullptr && ranges == nullptr && counts == nullptr) { return GCSA2_OK; }
+  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
+                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
+  const u64 pieces = cut.size() - 1;
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  return fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard guard(ix->device);
+    std::vector<u64> local;
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      const u64 at = woff[b], windows = woff[b + count] - at;
+      rebase_piece(offsets, b, count, local);
+      Lease lease(ix);
+      hipError_t e = lease.begin(Lease::need(bytes + 16) + Lease::need((count + 1) * 8) + (profiles != nullptr ? Lease::need(count * 32) : 0) +
+                                 (ranges != nullptr ? Lease::need(windows * 16) : 0) + (counts != nullptr ? Lease::need(windows * 8) : 0));
+      if(e != hipSuccess) { out.set(GCSA2_ERR_OUT_OF_MEMORY, std::string("staging of a piece: ") + hipGetErrorString(e)); break; }
+      u8* d_pat = lease.dev<u8>(bytes + 16); u64* d_off = lease.dev<u64>(count + 1);
+      gcsa2_kmer_profile* d_prof = (profiles != nullptr ? lease.dev<gcsa2_kmer_profile>(count) : nullptr);
+      u64* d_rng = (ranges != nullptr ? lease.dev<u64>(2 * windows) : nullptr);
+      u64* d_cnt = (counts != nullptr ? lease.dev<u64>(windows) : nullptr);
+      e = lease.up(d_pat, patterns + first, bytes);
+      if(e == hipSuccess) { e = lease.up(d_off, local.data(), (count + 1) * sizeof(u64)); }
+      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
+      u64 got = 0;
+      const int piece_rc = gcsa2_kmer_windows_device(ix, d_pat, d_off, count, k, stride, flags, nullptr, d_prof, d_rng, d_cnt, windows, &got, lease.stream());
+      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
+      if(profiles != nullptr) { e = lease.down(profiles + b, d_prof, count * sizeof(gcsa2_kmer_profile)); }
+      if(e == hipSuccess && ranges != nullptr) { e = lease.down(ranges + 2 * at, d_rng, 2 * windows * sizeof(u64)); }
+      if(e == hipSuccess && counts != nullptr) { e = lease.down(counts + at, d_cnt, windows * sizeof(u64)); }
+      if(e == hipSuccess) { e = lease.finish(); }
+      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
+    }
+  });
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_windows_batch: ") + e.what()); }
 }
 
 }  // extern "C"

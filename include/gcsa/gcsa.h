@@ -134,6 +134,40 @@ public:
     return result;
   }
 
+  // Batched k-mer windows (gcsa2_kmer_windows_batch): find() -- and with `counts` count() -- of every window
+  // P_q[j stride, j stride + k) of every read, without copying the windows out.  window_offsets (reads + 1) is the exclusive
+  // prefix sum of the windows per read; profiles[q] = { windows, found, nodes, occurrences } of read q (occurrences only
+  // with `counts`); ranges / counts are per window, in read order.  What was not asked for stays empty.
+  struct KMerWindows
+  {
+    std::vector<size_type> window_offsets;
+    std::vector<gcsa2_kmer_profile> profiles;
+    std::vector<range_type> ranges;
+    std::vector<size_type> counts;
+  };
+  KMerWindows kmer_windows_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k,
+                                 size_type stride = 1, bool counts = false, bool ranges = true, bool profiles = true) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    const int flags = (counts ? GCSA2_KMER_COUNTS : 0);
+    const std::uint8_t dummy = 0;
+    const std::uint8_t* data = patterns.empty() ? &dummy : patterns.data();
+    KMerWindows result;
+    result.window_offsets.assign(np + 1, 0);
+    size_type total = 0;      // the offsets alone first: they size the per-window arrays (host arithmetic, no device work)
+    check(gcsa2_kmer_windows_batch(handle, data, offsets.data(), np, k, stride, flags, result.window_offsets.data(), nullptr, nullptr,
+                                   nullptr, 0, &total), "GCSA::kmer_windows_batch()");
+    if(profiles) { result.profiles.resize(np); }
+    if(ranges) { result.ranges.resize(total); }
+    if(counts) { result.counts.resize(total); }
+    if(!profiles && !ranges && !counts) { return result; }
+    static_assert(sizeof(range_type) == 2 * sizeof(size_type), "range_type must be two packed u64");
+    check(gcsa2_kmer_windows_batch(handle, data, offsets.data(), np, k, stride, flags, nullptr, profiles ? result.profiles.data() : nullptr,
+                                   ranges ? reinterpret_cast<size_type*>(result.ranges.data()) : nullptr,
+                                   counts ? result.counts.data() : nullptr, total, &total), "GCSA::kmer_windows_batch()");
+    return result;
+  }
+
   // Batched find of k-mers handed over as 2-bit codes (gcsa2_find_batch_packed: `length` characters each, last character
   // first, comp - 1 in two bits, ceil(length / 32) words per pattern): 8 instead of 40 bytes per 32-mer over the link.
   std::vector<range_type> find_packed_batch(const std::vector<std::uint64_t>& codes, size_type length) const

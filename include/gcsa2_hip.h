@@ -300,6 +300,60 @@ int gcsa2_extend_device(const gcsa2_index* index, const uint8_t* d_patterns, con
 int gcsa2_extend_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
                        const gcsa2_search_state* states, uint64_t n_states, gcsa2_extension* out);
 
+/* ---- k-mer windows: find() and count() of every k-mer of every read, with per-read profiles --------------------------------
+ * A pattern set of gcsa2_find_device cannot hold overlapping patterns, so a k-mer user (genotyping, read screening, seed
+ * weighting) would have to copy every window out.  Here the reads are the pattern set and the windows are implied.
+ * (d_patterns, d_offsets, n_patterns) is the pattern CSR of gcsa2_find_device; k >= 1 is the window length, stride >= 1.
+ *
+ * DEFINITION.  For read q = P_q of length L:
+ *   - W_q = 0 windows if L < k, else (L - k) / stride + 1; window j of read q is P_q[j stride, j stride + k).
+ *   - Its global index is w = window_offsets[q] + j, window_offsets being the exclusive prefix sum of W_q (n_patterns + 1
+ *     entries; the last one is the total).
+ *   - range(w) = (d_ranges[2w], d_ranges[2w + 1]) is exactly what gcsa2_find_device returns for that substring handed over as
+ *     a pattern of its own, bit for bit, both empty forms included: the empty charRange of the last character, and the
+ *     edge-space integers of the LF step that emptied the range (gcsa.h:160).
+ *   - count(w) = d_counts[w] = GCSA::count(range(w)) (src/gcsa.cpp:802-809; 0 for an empty range).
+ *   - profile(q) = { windows = W_q, found = the number of non-empty ranges among the read's windows, nodes = the sum of
+ *     Range::length over those, occurrences = the sum of count(w) }; occurrences is 0 without GCSA2_KMER_COUNTS.
+ * k may exceed gcsa2_order(): the results are find()'s, false positives included (a path of the graph need not spell a
+ * k-mer longer than the order), exactly as for gcsa2_find_device.
+ *
+ * Outputs.  Any of d_window_offsets, d_profiles, d_ranges, d_counts may be NULL; the library keeps the window offsets in
+ * stream-ordered scratch when the caller does not want them, and zeroes the profiles itself.  `capacity` is the number of
+ * windows d_ranges / d_counts hold (ignored when both are NULL).  *total_windows is always the number needed; when d_ranges
+ * or d_counts is given and it exceeds capacity the call fails with GCSA2_ERR_BUFFER_TOO_SMALL: d_window_offsets (if given)
+ * is complete then, and nothing is written into d_ranges, d_counts or d_profiles.  Nothing is ever written behind a capacity.
+ * GCSA2_ERR_INVALID_ARGUMENT, with nothing written and before any device is touched: k == 0, stride == 0, d_counts without
+ * GCSA2_KMER_COUNTS, an unknown flag, a NULL index (or a NULL total_windows).  GCSA2_KMER_COUNTS on an image without counters:
+ * GCSA2_ERR_MISSING_COMPONENT, likewise.
+ *
+ * The device form follows the buffer conventions at the top of this header; no pattern byte outside the 8-byte words that
+ * hold [d_offsets[0], d_offsets[n_patterns]) is read, whatever k and the read lengths are.  It reads *total_windows back
+ * once, so it is enqueued on `stream` and complete on return, like gcsa2_mem_hits_device.  One call takes fewer than 2^32
+ * windows: more is refused with GCSA2_ERR_BUFFER_TOO_SMALL ("split the batch"; *total_windows is still the number,
+ * d_window_offsets complete, nothing else written), and 2^32 reads or more likewise, before any work (*total_windows = 0,
+ * nothing written).  The jump table of a find-only image is not
+ * consulted (the ranges are find()'s either way); pair blocks and the seed table are used as find() uses them.
+ *
+ * The host form requires offsets[0] == 0 and refuses decreasing offsets (GCSA2_ERR_INVALID_ARGUMENT).  It knows the total
+ * before any device work, so on GCSA2_ERR_BUFFER_TOO_SMALL it writes nothing at all but *total_windows.  A batch of 64 MB of
+ * reads or more travels in pieces of whole reads (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS, as the MEM calls); windows, counts and
+ * profiles keep the order of the reads.  With profiles as the only output a piece moves its reads (bytes and offsets) in and
+ * 32 bytes per read out, and nothing else. */
+typedef struct gcsa2_kmer_profile { uint64_t windows, found, nodes, occurrences; } gcsa2_kmer_profile;
+#define GCSA2_KMER_COUNTS 1   /* evaluate count(): d_counts and profile.occurrences; needs the counters */
+int gcsa2_kmer_windows_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                              uint64_t k, uint64_t stride, int flags,
+                              uint64_t* d_window_offsets,        /* n_patterns + 1, or NULL */
+                              gcsa2_kmer_profile* d_profiles,    /* n_patterns, or NULL */
+                              uint64_t* d_ranges,                /* 2 per window, or NULL */
+                              uint64_t* d_counts,                /* 1 per window, or NULL */
+                              uint64_t capacity,                 /* windows that d_ranges / d_counts hold */
+                              uint64_t* total_windows, void* stream);
+int gcsa2_kmer_windows_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                             uint64_t k, uint64_t stride, int flags, uint64_t* window_offsets, gcsa2_kmer_profile* profiles,
+                             uint64_t* ranges, uint64_t* counts, uint64_t capacity, uint64_t* total_windows);
+
 /* ---- count: GCSA::count(range) (src/gcsa.cpp:802-809) -------------------------------------- */
 int gcsa2_count_batch(const gcsa2_index* index, const uint64_t* ranges, uint64_t n_queries,
                       uint64_t* counts);
