@@ -68,7 +68,7 @@ __global__ __launch_bounds__(TPB) void k_seed_level(DevImage img, u32 j, u64 fir
 // ds_read_b128 read-back is conflict free) and every lane then evaluates its own
 // C[c] + rank(B_c, .) and rank(edges, .) from the staged block.  A second fetch round runs only
 // for lanes whose sp and ep + 1 fall into different blocks.
-constexpr int TPB2 = 128;          // 2 waves: 16 KB of staging + tables -> 9 workgroups / CU
+constexpr int TPB2 = 128;          // 2 waves: 16 KB of staging + tables (+ 1 KB of block addresses in the JUMP form of k_find2) -> 9 workgroups / CU
 
 struct Tables2
 {
@@ -243,7 +243,9 @@ __device__ __forceinline__ void fetch_blocks(const u64* __restrict__ flb, u32 id
 // The same fetch with gfx950's direct global -> LDS loads (global_load_lds_dwordx4; the matching statistics use it, round 4): no
 // destination registers -- the eight requests of a wave are in flight without the 32 VGPRs the register form keeps for them
 // (k_match_stats2: 123 -> 109 VGPRs), and the request can be ISSUED long before its data is needed (fetch_blocks_issue ...
-// fetch_blocks_wait).  find() keeps the register form: same speed there (20.2-20.4 ms either way), it is bound by the request rate.  The instruction writes lane L's
+// fetch_blocks_wait).  k_find2 without the jump table keeps the register form: same speed there (20.2-20.4 ms either way), it sits at the
+// memory system's request rate.  Its JUMP instantiations take this form together with eval_staged: below that rate the 64 registers
+// of the fetch and of the copy out of LDS were what it paid for (110 -> 69 VGPRs, 16.2 -> 14.5 ms per step; profiles/find_lds_stage.md).  The instruction writes lane L's
 // 16 bytes at M0 + 16 L, i.e. linearly; the XOR swizzle of the slots therefore moves to the SOURCE side: the lane at
 // position `sub` of an owner's slot loads chunk sub ^ (owner & 7) of the block, which is the same layout as above.
 template<bool PAIR = false, bool LCPW = false>
@@ -363,6 +365,11 @@ __device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 after2, u
 // waves per CU that LDS allows -- measured 2-5 % SLOWER (profiles/r02_occupancy.md): at 16 waves the kernel already sits at
 // the memory system's request rate, more resident chains only lengthen each one's round trip.
 constexpr int FIND_WAVES = 4;
+// The JUMP instantiations (find-only images) fetch and evaluate through LDS alone (fetch_blocks_direct, eval_staged): 69 VGPRs
+// would allow 7 waves per SIMD, the 17.5 KB of LDS per workgroup allow 9 workgroups = 18 waves per CU, i.e. 5 on two SIMDs
+// and 4 on the others.  Stages of 48, 40 and 32 slots per wave (20 - 28 waves per CU) ran at the same speed as this one:
+// resident waves are not what limits the kernel (profiles/find_lds_stage.md).
+constexpr int JUMP_WAVES = 5;
 // PACKED = true (gcsa2_find_packed_device): the patterns arrive as 2-bit codes, all of one length `offsets` (the argument is
 // then the LENGTH, not an array), last character first -- word j of pattern q, at patterns + 8 (q W + j) with W = ceil(length /
 // 32), holds the characters at distance 32 j .. 32 j + 31 from the pattern's end, comp - 1 of the character at distance t in
@@ -370,7 +377,7 @@ constexpr int FIND_WAVES = 4;
 // sends 8 bytes per 32-mer over the link instead of 32 + 8; the kernel's seed index and pattern window are the words
 // themselves.  Only fast characters can be written this way (comps 1..4: a pattern with an N takes the byte interface).
 template<bool STATS, bool JUMP = false, bool PAIR = false, bool PACKED = false>
-__global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : FIND_WAVES) void k_find2(DevImage img, const u8* __restrict__ patterns,
+__global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES)) void k_find2(DevImage img, const u8* __restrict__ patterns,
                                                const u64* __restrict__ offsets, u64 nq,
                                                u64* __restrict__ out, unsigned long long* __restrict__ stats,
                                                const u32* __restrict__ perm)
@@ -385,6 +392,12 @@ __global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : FIND_WAVES) void k_find
 
   const u32 lane = threadIdx.x & 63;
   ulonglong2* wave_stage = stage + (threadIdx.x & ~63u) * 8;
+  [[maybe_unused]] u64* wave_addr = nullptr;   // JUMP: the block address of every lane, for the eight lanes that fetch it (fetch_blocks_issue)
+  if constexpr(JUMP)
+  {
+    __shared__ u64 addr_table[TPB2];
+    wave_addr = addr_table + (threadIdx.x & ~63u);
+  }
   u64 blocks = 0, steps = 0, lookups = 0, jumps = 0;
   [[maybe_unused]] u64 fetch_steps = 0, second_fetches = 0, wide_seeds = 0;     // STATS only
   [[maybe_unused]] unsigned int* touched = nullptr;
@@ -574,31 +587,52 @@ __global__ __launch_bounds__(TPB2, (STATS || JUMP) ? 4 : FIND_WAVES) void k_find
         if(need2) { const u32 b = (idx_ep & PAIR_FLAG) ? singles + (idx_ep & ~PAIR_FLAG) : idx_ep; atomicOr(touched + (b >> 5), 1u << (b & 31)); }
       }
     }
-    ulonglong2 blk[8];
-    fetch_blocks<PAIR>(img.flb, idx_sp, stepping, wave_stage, lane, img.flp);
-    if(stepping)
+    if constexpr(JUMP)
     {
-      read_block(wave_stage, lane, blk);
-      if(PAIR && pair)
+      // No destination registers and no copy of the block: the requests go straight into the wave's slots in LDS and every
+      // lane evaluates its endpoints from its slot (fetch_blocks_direct, eval_staged).  The jump entry above was requested
+      // first and is read after the blocks have landed.
+      fetch_blocks_direct<PAIR>(img.flb, idx_sp, stepping, wave_stage, lane, img.flp, nullptr, wave_addr);
+      if(stepping)
       {
-        p_sp = eval_pair(blk, r_sp, false);
-        if(idx_ep == idx_sp) { p_ep = eval_pair(blk, r_ep, true); }
+        p_sp = eval_staged(wave_stage, lane, PAIR && pair, r_sp, false);          // gcsa.h:271, then rank(edges, sp')
+        if(idx_ep == idx_sp) { p_ep = eval_staged(wave_stage, lane, PAIR && pair, r_ep, true); }
       }
-      else
+      if(__any(need2))
       {
-        eval_endpoint(blk, r_sp, 0, p_sp.raw, p_sp.node);      // gcsa.h:271, then rank(edges, sp')
-        if(idx_ep == idx_sp) { eval_endpoint(blk, r_ep, 1, p_ep.raw, p_ep.node); }
+        // fetch_blocks_issue waits for the LDS reads above (lgkmcnt(0), wave barrier) before a request overwrites a slot
+        fetch_blocks_direct<PAIR>(img.flb, idx_ep, need2, wave_stage, lane, img.flp, nullptr, wave_addr);
+        if(need2) { p_ep = eval_staged(wave_stage, lane, PAIR && pair, r_ep, true); }   // gcsa.h:272: LF(ep + 1) - 1 (.raw is that + 1)
       }
     }
-    if(__any(need2))
+    else
     {
-      __builtin_amdgcn_wave_barrier();
-      fetch_blocks<PAIR>(img.flb, idx_ep, need2, wave_stage, lane, img.flp);
-      if(need2)
+      ulonglong2 blk[8];
+      fetch_blocks<PAIR>(img.flb, idx_sp, stepping, wave_stage, lane, img.flp);
+      if(stepping)
       {
         read_block(wave_stage, lane, blk);
-        if(PAIR && pair) { p_ep = eval_pair(blk, r_ep, true); }
-        else { eval_endpoint(blk, r_ep, 1, p_ep.raw, p_ep.node); }   // gcsa.h:272: LF(ep + 1) - 1
+        if(PAIR && pair)
+        {
+          p_sp = eval_pair(blk, r_sp, false);
+          if(idx_ep == idx_sp) { p_ep = eval_pair(blk, r_ep, true); }
+        }
+        else
+        {
+          eval_endpoint(blk, r_sp, 0, p_sp.raw, p_sp.node);      // gcsa.h:271, then rank(edges, sp')
+          if(idx_ep == idx_sp) { eval_endpoint(blk, r_ep, 1, p_ep.raw, p_ep.node); }
+        }
+      }
+      if(__any(need2))
+      {
+        __builtin_amdgcn_wave_barrier();
+        fetch_blocks<PAIR>(img.flb, idx_ep, need2, wave_stage, lane, img.flp);
+        if(need2)
+        {
+          read_block(wave_stage, lane, blk);
+          if(PAIR && pair) { p_ep = eval_pair(blk, r_ep, true); }
+          else { eval_endpoint(blk, r_ep, 1, p_ep.raw, p_ep.node); }   // gcsa.h:272: LF(ep + 1) - 1
+        }
       }
     }
     __builtin_amdgcn_wave_barrier();
