@@ -16,6 +16,7 @@
 //                       k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
 //   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
+//                       k_kmer_seeds          the same search, emitting the found windows as seed records (gcsa2_kmer_hits_device)
 //                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
@@ -5246,6 +5247,265 @@ int gcsa2_kmer_windows_batch(const gcsa2_index* ix, const uint8_t* patterns, con
     }
   });
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_windows_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== k-mer hits: the found windows of every read as seeds with count() and locate() (kernels_windows.hpp, kernels_mem.hpp) ====
+namespace {
+
+// what both forms refuse before any device is touched, then the components the call needs (no LCP array)
+int kmer_hits_checks(const gcsa2_index* ix, u64 k, u64 stride, int over, const u64* total_seeds, const u64* total_hits)
+{
+  CHECK_INDEX(ix);
+  if(total_seeds == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_hits: k must be at least 1"); }
+  if(stride == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_hits: stride must be at least 1"); }
+  if(over != GCSA2_MEM_OVER_SKIP && over != GCSA2_MEM_OVER_SAMPLE)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_hits: unknown over-cap policy (GCSA2_MEM_OVER_SKIP or GCSA2_MEM_OVER_SAMPLE)");
+  }
+  return locate_checks(ix, 0);
+}
+
+// gcsa2_kmer_hits_device after its argument checks (0 < n_patterns < 2^32).  Host round trips: the number of windows, the
+// number of seeds (twice when the arrival area was too small for them), those of the shared tail, the end.
+// Scratch: per read the window offsets and, if asked for, the profiles (the caller's only once everything fits); per 64
+// windows the owner entry and 16 bytes of SeedEmit; the rest per seed.
+int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max, int over,
+                   gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
+                   u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *sizes = nullptr, *woff = nullptr;
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  HIP_TRY(scratch.get(woff, n_patterns + 1));
+  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
+  LAUNCH_CHECK("k_window_counts");
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  u64 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if(total >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more windows in one call; split the batch"); }
+  // no seed: zeroed offsets, the profiles are their window numbers
+  auto nothing_found = [&](const gcsa2_kmer_profile* prof) -> int
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, (n_patterns + 1) * sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    if(d_profiles != nullptr)
+    {
+      if(prof != nullptr) { HIP_TRY(hipMemcpyAsync(d_profiles, prof, n_patterns * sizeof(gcsa2_kmer_profile), hipMemcpyDeviceToDevice, st)); }
+      else { HIP_TRY(hipMemsetAsync(d_profiles, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    return GCSA2_OK;
+  };
+  if(total == 0) { return nothing_found(nullptr); }
+  // 1. the search: seed records in arrival order, the profiles in scratch
+  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
+  u64* owners = nullptr;
+  gcsa2_kmer_profile* prof = nullptr;
+  SeedEmit emit{};
+  HIP_TRY(scratch.get(owners, spans + 1));
+  HIP_TRY(scratch.get(emit.cursor, 1));
+  HIP_TRY(scratch.get(emit.base, spans));
+  HIP_TRY(scratch.get(emit.found, spans + 1));
+  HIP_TRY(scratch.get(emit.mask, spans));
+  if(d_profiles != nullptr) { HIP_TRY(scratch.get(prof, n_patterns)); }
+  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
+  LAUNCH_CHECK("k_block_owners");
+  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
+  u64 m = 0;
+  emit.capacity = std::min(seed_capacity, total);
+  for(int attempt = 0; attempt < 2; attempt++)
+  {
+    HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
+    HIP_TRY(scratch.get(emit.counts, emit.capacity));
+    HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(emit.found + spans, 0, sizeof(u32), st));
+    if(prof != nullptr) { HIP_TRY(hipMemsetAsync(prof, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
+    if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
+    else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
+    LAUNCH_CHECK("k_kmer_seeds");
+    HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if(m <= emit.capacity || attempt == 1) { break; }
+    emit.capacity = m;        // the caller's capacity is short: the records are still needed, for *total_hits
+  }
+  if(m > emit.capacity) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "kmer_hits: two runs of the search disagree on the number of seeds"); }
+  *total_seeds = m;
+  if(m == 0) { return nothing_found(prof); }
+  // 2. window order: the scan of the wavefronts' found numbers, then every wavefront's records to their place
+  u64 *recs = nullptr, *counts = nullptr;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, emit.found, emit.found, size_t(spans + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, emit.found, emit.found, size_t(spans + 1), st));
+  HIP_TRY(scratch.get(recs, 4 * m));
+  HIP_TRY(scratch.get(counts, m));
+  hipLaunchKernelGGL(k_seed_place, dim3(grid_for(spans * 64)), dim3(TPB), 0, st, emit.base, emit.found, spans, emit.recs, emit.counts, recs, counts);
+  LAUNCH_CHECK("k_seed_place");
+  // 3. count class, locate, hits in seed order (mem_hits' tail); offsets and profiles only once everything fits
+  const int rc = mem_hits_tail(ix, recs, counts, m, hit_max, over, d_seeds, seed_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  scratch.settled = false;
+  hipLaunchKernelGGL(k_seed_offsets, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, woff, n_patterns, total, spans, emit.found, emit.mask, d_seed_offsets);
+  LAUNCH_CHECK("k_seed_offsets");
+  if(d_profiles != nullptr) { HIP_TRY(hipMemcpyAsync(d_profiles, prof, n_patterns * sizeof(gcsa2_kmer_profile), hipMemcpyDeviceToDevice, st)); }
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                           uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* d_profiles, uint64_t* d_seed_offsets,
+                           gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* d_hit_offsets, uint64_t* d_hits,
+                           uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  int rc = kmer_hits_checks(ix, k, stride, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(d_seed_offsets == nullptr || d_hit_offsets == nullptr || (n_patterns > 0 && d_offsets == nullptr) || (d_seeds == nullptr && seed_capacity > 0) ||
+     (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  return kmer_hits_core(ix, d_patterns, d_offsets, n_patterns, k, stride, hit_max, over, d_profiles, d_seed_offsets, d_seeds, seed_capacity, total_seeds,
+                        d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_device: ") + e.what()); }
+}
+
+// The host form.  One piece: copied in, run on device buffers of the caller's capacities, copied out only when everything fits.
+// A batch of two pieces' worth of read bytes or more is cut into pieces of whole reads (tune.ms_piece_bytes, cut_pieces) that
+// tune.ms_threads host threads carry; the number of seeds of a piece is not known before it ran, so every piece keeps its four
+// arrays in host memory (sized from a first refusal of the device form) and the caller's arrays are put together from them in
+// read order at the end, when the totals are known to fit.
+int gcsa2_kmer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                          uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles, uint64_t* seed_offsets,
+                          gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* hit_offsets, uint64_t* hits,
+                          uint64_t hit_capacity, uint64_t* total_hits)
+{
+  int rc = kmer_hits_checks(ix, k, stride, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(seed_offsets == nullptr || hit_offsets == nullptr || (n_patterns > 0 && offsets == nullptr) || (seeds == nullptr && seed_capacity > 0) ||
+     (hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more reads in one call; split the batch"); }
+  if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  u64 windows_all = 0;
+  for(u64 q = 0; q < n_patterns; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    if(len >= k) { windows_all += (len - k) / stride + 1; }
+  }
+  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more windows in one call; split the batch"); }
+  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
+                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
+  const u64 pieces = cut.size() - 1;
+  struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
+  std::vector<Piece> done(pieces);
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard guard(ix->device);
+    std::vector<u64> local;
+    hipStream_t stream = nullptr;
+    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      u64 windows = 0;
+      for(u64 q = 0; q < count; q++) { const u64 len = local[q + 1] - local[q]; if(len >= k) { windows += (len - k) / stride + 1; } }
+      Piece& piece = done[c];
+      DBuf<u8> d_pat; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds; DBuf<gcsa2_kmer_profile> d_prof;
+      hipError_t e = d_pat.alloc(bytes + 16);
+      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
+      if(e == hipSuccess) { e = d_seed_off.alloc(count + 1); }
+      if(e == hipSuccess && profiles != nullptr) { e = d_prof.alloc(count); }
+      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
+      // one piece: the caller's capacities (a refusal is the call's); several: room for every window, so that the search runs
+      // once, and an estimate of the hits, then what the refusal asks for
+      u64 rm = (pieces == 1 ? std::min(seed_capacity, windows) : windows), rh = (pieces == 1 ? hit_capacity : 4 * rm);
+      int piece_rc = GCSA2_OK;
+      for(int attempt = 0; attempt < 2; attempt++)
+      {
+        d_seeds.release(); d_hit_off.release(); d_hits.release();
+        e = d_seeds.alloc(rm);
+        if(e == hipSuccess) { e = d_hit_off.alloc(rm + 1); }
+        if(e == hipSuccess) { e = d_hits.alloc(rh); }
+        if(e != hipSuccess) { break; }
+        piece_rc = gcsa2_kmer_hits_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, over, d_prof.p, d_seed_off.p, d_seeds.p, rm, &piece.m,
+                                          d_hit_off.p, d_hits.p, rh, &piece.h, stream);
+        if(piece_rc == GCSA2_ERR_BUFFER_TOO_SMALL && pieces > 1 && attempt == 0 && (piece.m > rm || piece.h > rh)) { rm = piece.m; rh = piece.h; continue; }
+        break;
+      }
+      if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); break; }
+      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
+      piece.seed_off.resize(count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
+      e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
+      if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && profiles != nullptr) { e = hipMemcpy(profiles + b, d_prof.p, count * sizeof(gcsa2_kmer_profile), hipMemcpyDeviceToHost); }
+      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
+    }
+    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+  });
+  u64 m = 0, h = 0;
+  for(const Piece& piece : done) { m += piece.m; h += piece.h; }
+  *total_seeds = m;
+  *total_hits = h;
+  if(rc != GCSA2_OK) { return rc; }
+  if(m > seed_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed buffer too small"); }
+  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
+  u64 mbase = 0, hbase = 0;
+  for(u64 c = 0; c < pieces; c++)
+  {
+    const Piece& piece = done[c];
+    const u64 b = cut[c], count = cut[c + 1] - b;
+    for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
+    if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
+    for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }
+    if(piece.h > 0) { std::memcpy(hits + hbase, piece.hits.data(), piece.h * sizeof(u64)); }
+    mbase += piece.m;
+    hbase += piece.h;
+  }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_batch: ") + e.what()); }
 }
 
 }  // extern "C"

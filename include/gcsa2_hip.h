@@ -674,6 +674,57 @@ int gcsa2_sub_mem_hits_batch(const gcsa2_index* index, const uint8_t* patterns, 
                              uint64_t min_length, uint64_t reseed_length, uint64_t hit_max, int over,
                              uint64_t* sub_offsets, gcsa2_mem* subs, uint64_t sub_capacity, uint64_t* total_subs,
                              uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* ---- k-mer hits: the k-mers of every read that occur, as seeds with count() and their positions ----------------------------
+ * What lies between gcsa2_kmer_windows_device (every window, found or not, 24 bytes each) and gcsa2_mem_hits_device (seeds
+ * with hits, but MEMs): the found windows only, compacted, in read order, with count() and hits, in one call -- a k-mer
+ * seeding mapper's or a genotyper's lookup.  (d_patterns, d_offsets, n_patterns), k and stride are those of
+ * gcsa2_kmer_windows_device; hit_max and over those of gcsa2_mem_hits_device.
+ *
+ * DEFINITION.
+ *   - The windows are exactly those of gcsa2_kmer_windows_device for (k, stride): window j of read q is P_q[j stride, j stride + k).
+ *   - The seeds of read q are its windows with a non-empty range, in ascending window order:
+ *     d_seeds[d_seed_offsets[q] .. d_seed_offsets[q + 1]) (n_patterns + 1 offsets; the last one is the total).
+ *   - Each seed is the record { position = j stride (within the read), length = k, sp, ep, count }: (sp, ep) is bit for bit
+ *     what gcsa2_find_device returns for that substring, count = GCSA::count(sp, ep).  A window with an empty range -- either
+ *     empty form -- makes no record.
+ *   - The record type is gcsa2_mem on purpose: a seed CSR is a valid input to gcsa2_sub_mem_hits_device and to everything else
+ *     a caller has for MEMs.
+ *   - Hits of seed i: d_hits[d_hit_offsets[i] .. d_hit_offsets[i + 1]) (seed_capacity + 1 offsets), by the rules of
+ *     gcsa2_mem_hits_device, word for word: hit_max == 0 (no cap) or count <= hit_max: the sorted distinct values of
+ *     gcsa2_locate_into(sort = 1); otherwise GCSA2_MEM_OVER_SKIP: none (the seed and its count are still reported), or
+ *     GCSA2_MEM_OVER_SAMPLE: the values of gcsa2_locate_max(range, hit_max), value for value and in order; its
+ *     INVALID_ARGUMENT for a range the reference would draw forever on is passed through.
+ *   - d_profiles, if given (n_patterns entries), equals what gcsa2_kmer_windows_device returns with GCSA2_KMER_COUNTS.
+ *
+ * *total_seeds and *total_hits are always the sizes needed; if either exceeds its capacity the call fails with
+ * GCSA2_ERR_BUFFER_TOO_SMALL and writes nothing into d_seeds, d_hit_offsets, d_hits or d_profiles (nor, as it stands, into
+ * d_seed_offsets).  Nothing is ever written behind a capacity.  seed_capacity equal to the number of windows always suffices.
+ * Limits and refusals are those of gcsa2_kmer_windows_device: 2^32 windows or reads, GCSA2_ERR_BUFFER_TOO_SMALL ("split the
+ * batch"), nothing written.  GCSA2_ERR_INVALID_ARGUMENT, with nothing written and before any device is touched: k == 0,
+ * stride == 0, an unknown `over`, a NULL index (or a NULL total pointer).  Needs the samples and the counters
+ * (GCSA2_ERR_MISSING_COMPONENT, likewise); unlike MEM hits it does not need the LCP array.  n_patterns == 0, no window at all
+ * and no found window are GCSA2_OK: the seed offsets are zeroed and d_hit_offsets[0] = 0.  d_seeds / d_hits may be NULL with a
+ * capacity of 0 (a sizing call).  Enqueued on `stream`, complete on return.
+ *
+ * No per-window range or count buffer exists: the search kernel ranks the found lanes of a wavefront, reserves their records
+ * with one atomic add and writes them in arrival order; a scan and a second small kernel put them into window order.  Device
+ * scratch per call: the window offsets (and the profiles, if asked for) per read, 8 + 16 bytes per 64 windows, the rest per
+ * seed.  A seed_capacity below *total_seeds makes the call search twice (the records are needed for *total_hits). */
+int gcsa2_kmer_hits_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                           uint64_t k, uint64_t stride, uint64_t hit_max, int over,
+                           gcsa2_kmer_profile* d_profiles,                 /* n_patterns, or NULL */
+                           uint64_t* d_seed_offsets,                       /* n_patterns + 1 */
+                           gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                           uint64_t* d_hit_offsets,                        /* seed_capacity + 1 */
+                           uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+/* The same for a batch in host memory: offsets[0] == 0, decreasing offsets are refused (GCSA2_ERR_INVALID_ARGUMENT).  A batch
+ * of two pieces' worth of read bytes or more travels in pieces of whole reads (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS, as the MEM
+ * calls); seeds, hit offsets and hits keep read order across pieces.  On GCSA2_ERR_BUFFER_TOO_SMALL a batch in one piece
+ * writes nothing; one in pieces leaves the result arrays unspecified, as gcsa2_mem_hits_batch.  Complete on return. */
+int gcsa2_kmer_hits_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                          uint64_t k, uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles,
+                          uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                          uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
