@@ -44,6 +44,7 @@ EXPORTS = [
     "gcsa2_match_breaks_bounded_device", "gcsa2_match_breaks_bounded_batch", "gcsa2_mem_hits_bounded_device", "gcsa2_mem_hits_bounded_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
     "gcsa2_extend_device", "gcsa2_extend_batch", "gcsa2_kmer_windows_device", "gcsa2_kmer_windows_batch",
     "gcsa2_kmer_hits_device", "gcsa2_kmer_hits_batch",
+    "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -167,6 +168,8 @@ def load_library():
     L.gcsa2_kmer_windows_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, C.c_int, vp, vp, vp, vp, u64, u64p]
     L.gcsa2_kmer_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_kmer_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
+    L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
     L.gcsa2_group_destroy.argtypes = [vp]
     L.gcsa2_group_destroy.restype = None
@@ -574,6 +577,67 @@ class GCSA:
         rc = self._L.gcsa2_kmer_hits_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), over, d_profiles or None,
                                             d_seed_offsets, d_seeds or None, int(seed_capacity), C.byref(total_m), d_hit_offsets, d_hits or None,
                                             int(hit_capacity), C.byref(total_h), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_m.value, total_h.value)
+            raise err
+        return total_m.value, total_h.value
+
+    def capped_seeds_batch(self, patterns, offsets, min_length, max_length=0, max_count=1, hit_max=0, sample=False, out=None):
+        """The shortest matches of every read that occur at most max_count times, with counts and positions
+        (gcsa2_capped_seeds_batch): (seed_offsets (reads + 1), seeds (total, 5) = {position, length, sp, ep, count}, hit_offsets
+        (total + 1), hits).  From the end of a read the match is extended until it has min_length characters and count() <=
+        max_count, emitted, and the search starts again behind it; max_length (0: none) cuts an attempt short.  The seeds of a
+        read do not overlap and come in descending position; a seed's hits follow mem_hits_batch's rules (hit_max, sample).
+        The rows of `seeds` are MEM records: sub_mem_hits_batch takes them as they are.  Needs no LCP array.  The buffers are
+        sized from a first refusal.  `out` = (seed_offsets, seeds, hit_offsets, hits) arrays of the caller; too small ones
+        raise BUFFER_TOO_SMALL with `needed` = (seeds, hits)."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        over = 1 if sample else 0
+        total_m, total_h = C.c_uint64(), C.c_uint64()
+
+        def call(soff, seeds, hoff, hits):
+            assert soff.dtype == np.uint64 and soff.shape[0] >= n + 1 and seeds.dtype == np.uint64 and seeds.flags.c_contiguous
+            assert seeds.shape[1] == 5 and hoff.dtype == np.uint64 and hoff.shape[0] >= seeds.shape[0] + 1 and hits.dtype == np.uint64
+            return self._L.gcsa2_capped_seeds_batch(self._h, _p8(patterns), _p64(offsets), n, int(min_length), int(max_length), int(max_count),
+                                                    int(hit_max), over, soff.ctypes.data, seeds.ctypes.data, seeds.shape[0], C.byref(total_m),
+                                                    hoff.ctypes.data, hits.ctypes.data, hits.shape[0], C.byref(total_h))
+
+        if out is not None:
+            soff, seeds, hoff, hits = out
+            rc = call(soff, seeds, hoff, hits)
+        else:
+            mcap, hcap = 0, 0
+            soff = np.zeros(n + 1, dtype=np.uint64)
+            for _ in range(2):
+                seeds = np.zeros((mcap, 5), dtype=np.uint64)
+                hoff = np.zeros(mcap + 1, dtype=np.uint64)
+                hits = np.zeros(hcap, dtype=np.uint64)
+                rc = call(soff, seeds, hoff, hits)
+                if rc != STATUS_BUFFER_TOO_SMALL:
+                    break
+                mcap, hcap = max(mcap, total_m.value), max(hcap, total_h.value)
+        if rc == STATUS_BUFFER_TOO_SMALL:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_m.value, total_h.value)
+            raise err
+        _check(rc)
+        m, h = total_m.value, total_h.value
+        return soff[: n + 1], seeds[:m], hoff[: m + 1], hits[:h]
+
+    def capped_seeds_device(self, d_patterns, d_offsets, n_patterns, min_length, max_length, max_count, hit_max, sample, d_seed_offsets,
+                            d_seeds, seed_capacity, d_hit_offsets, d_hits, hit_capacity, stream=0):
+        """gcsa2_capped_seeds_device on caller-owned device buffers (raw pointers): d_seed_offsets n_patterns + 1 u64, d_seeds
+        seed_capacity records of five u64, d_hit_offsets seed_capacity + 1 entries, d_hits hit_capacity values.  `sample`: a
+        bool, or the `over` policy as an int.  Complete on return.  Returns (seeds, hits); raises Gcsa2Error (BUFFER_TOO_SMALL,
+        `.needed` = (seeds, hits)) when a buffer is too small."""
+        total_m, total_h = C.c_uint64(), C.c_uint64()
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        rc = self._L.gcsa2_capped_seeds_device(self._h, d_patterns, d_offsets, n_patterns, int(min_length), int(max_length), int(max_count),
+                                               int(hit_max), over, d_seed_offsets, d_seeds or None, int(seed_capacity), C.byref(total_m),
+                                               d_hit_offsets, d_hits or None, int(hit_capacity), C.byref(total_h), stream)
         if rc != 0:
             err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
             err.needed = (total_m.value, total_h.value)

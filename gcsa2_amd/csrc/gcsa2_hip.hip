@@ -18,6 +18,8 @@
 //   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
 //                       k_kmer_seeds          the same search, emitting the found windows as seed records (gcsa2_kmer_hits_device)
 //                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
+//   kernels_seeds.hpp   k_capped_seeds        GCSA::LF(range, comp) + GCSA::count per step: the shortest matches under an occurrence cap
+//                                                                        include/gcsa/gcsa.h:155-162, src/gcsa.cpp:802-809
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
 #include "sdsl_reader.hpp"
@@ -53,6 +55,7 @@ using namespace g2;
 #include "kernels_windows.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_submem.hpp"
+#include "kernels_seeds.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -5506,6 +5509,225 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const 
   }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== capped seeds: the shortest matches of every read that occur at most max_count times (kernels_seeds.hpp, kernels_mem.hpp) ====
+namespace {
+
+// what both forms refuse before any device is touched, then the components the call needs (no LCP array)
+int capped_seeds_checks(const gcsa2_index* ix, u64 min_length, u64 max_length, u64 max_count, int over, const u64* total_seeds, const u64* total_hits)
+{
+  CHECK_INDEX(ix);
+  if(total_seeds == nullptr || total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(min_length == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "capped_seeds: min_length must be at least 1"); }
+  if(max_count == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "capped_seeds: max_count must be at least 1"); }
+  if(max_length != 0 && min_length > max_length) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "capped_seeds: min_length exceeds max_length: no seed could be reported"); }
+  if(over != GCSA2_MEM_OVER_SKIP && over != GCSA2_MEM_OVER_SAMPLE)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "capped_seeds: unknown over-cap policy (GCSA2_MEM_OVER_SKIP or GCSA2_MEM_OVER_SAMPLE)");
+  }
+  return locate_checks(ix, 0);
+}
+
+// gcsa2_capped_seeds_device after its argument checks (0 < n_patterns < 2^32).  Host round trips: the seed total with the
+// overrun flag, those of the shared tail, the end.  Scratch: two words per read, the rest per seed.
+int capped_seeds_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 min_length, u64 max_length,
+                      u64 max_count, u64 hit_max, int over, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
+                      u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  unsigned long long* ctl = nullptr;
+  u64 *sizes = nullptr, *seed_off = nullptr;
+  HIP_TRY(scratch.get(ctl, SEEDS_CTL_WORDS));
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  HIP_TRY(scratch.get(seed_off, n_patterns + 1));
+  HIP_TRY(hipMemsetAsync(ctl, 0, SEEDS_CTL_WORDS * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(sizes, 0, (n_patterns + 1) * sizeof(u64), st));
+  // 1. the walk, counting; the CSR offsets; the walk again, writing (persistent lanes: what the device holds at once)
+  const u64 nr = (ix->img.n == 0 ? 0 : n_patterns);
+  const u64 resident = ix->tune.ms_grid != 0 ? ix->tune.ms_grid : u64(ix->compute_units) * 8;
+  const unsigned grid = unsigned(std::max<u64>(1, std::min<u64>((nr + TPB2 - 1) / TPB2, resident)));
+  const bool pair = (ix->img.flp != nullptr);          // the start of an attempt goes two characters per request
+  if(nr > 0)
+  {
+    if(pair) { hipLaunchKernelGGL((k_capped_seeds<false, true>), dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, nr, min_length, max_length, max_count, ctl, sizes, nullptr, nullptr, nullptr); }
+    else { hipLaunchKernelGGL((k_capped_seeds<false, false>), dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, nr, min_length, max_length, max_count, ctl, sizes, nullptr, nullptr, nullptr); }
+    LAUNCH_CHECK("k_capped_seeds<count>");
+  }
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, seed_off, size_t(n_patterns + 1), st));
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, seed_off, size_t(n_patterns + 1), st));
+  u64 m = 0;
+  unsigned long long words[SEEDS_CTL_WORDS];
+  HIP_TRY(hipMemcpyAsync(&m, seed_off + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(words, ctl, sizeof(words), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if(words[0] != 0) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "capped_seeds: a walk took more than 2 L + 2 LF steps for a read of L characters; the index is inconsistent"); }
+  *total_seeds = m;
+  if(m >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "capped_seeds: 2^32 or more seeds in one call; split the batch"); }
+  if(m == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, (n_patterns + 1) * sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    return GCSA2_OK;
+  }
+  u64 *recs = nullptr, *counts = nullptr;
+  HIP_TRY(scratch.get(recs, 4 * m));
+  HIP_TRY(scratch.get(counts, m));
+  HIP_TRY(hipMemsetAsync(ctl + 1, 0, sizeof(unsigned long long), st));
+  if(pair) { hipLaunchKernelGGL((k_capped_seeds<true, true>), dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, nr, min_length, max_length, max_count, ctl, nullptr, seed_off, recs, counts); }
+  else { hipLaunchKernelGGL((k_capped_seeds<true, false>), dim3(grid), dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, nr, min_length, max_length, max_count, ctl, nullptr, seed_off, recs, counts); }
+  LAUNCH_CHECK("k_capped_seeds<write>");
+  // 2. count class, locate, hits in seed order (mem_hits' tail); the offsets only once everything fits
+  const int rc = mem_hits_tail(ix, recs, counts, m, hit_max, over, d_seeds, seed_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  scratch.settled = false;
+  HIP_TRY(hipMemcpyAsync(d_seed_offsets, seed_off, (n_patterns + 1) * sizeof(u64), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_capped_seeds_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t min_length,
+                              uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over, uint64_t* d_seed_offsets, gcsa2_mem* d_seeds,
+                              uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity,
+                              uint64_t* total_hits, void* stream)
+{
+  int rc = capped_seeds_checks(ix, min_length, max_length, max_count, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(d_seed_offsets == nullptr || d_hit_offsets == nullptr || (n_patterns > 0 && d_offsets == nullptr) || (d_seeds == nullptr && seed_capacity > 0) ||
+     (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "capped_seeds: 2^32 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  return capped_seeds_core(ix, d_patterns, d_offsets, n_patterns, min_length, max_length, max_count, hit_max, over, d_seed_offsets, d_seeds, seed_capacity,
+                           total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_capped_seeds_device: ") + e.what()); }
+}
+
+// The host form.  One piece: copied in, run on device buffers of the caller's capacities, copied out only when everything fits.
+// A batch of two pieces' worth of read bytes or more is cut into pieces of whole reads (tune.ms_piece_bytes, cut_pieces) that
+// tune.ms_threads host threads carry, as gcsa2_kmer_hits_batch: every piece keeps its four arrays in host memory (sized from a
+// first refusal of the device form, whose sizing run keeps no records) and the caller's arrays are put together from them in
+// read order at the end, when the totals are known to fit.
+int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t min_length,
+                             uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over, uint64_t* seed_offsets, gcsa2_mem* seeds,
+                             uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity,
+                             uint64_t* total_hits)
+{
+  int rc = capped_seeds_checks(ix, min_length, max_length, max_count, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(seed_offsets == nullptr || hit_offsets == nullptr || (n_patterns > 0 && offsets == nullptr) || (seeds == nullptr && seed_capacity > 0) ||
+     (hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "capped_seeds: 2^32 or more reads in one call; split the batch"); }
+  if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
+                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
+  const u64 pieces = cut.size() - 1;
+  struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
+  std::vector<Piece> done(pieces);
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard guard(ix->device);
+    std::vector<u64> local;
+    hipStream_t stream = nullptr;
+    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      Piece& piece = done[c];
+      DBuf<u8> d_pat; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds;
+      hipError_t e = d_pat.alloc(bytes + 16);
+      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
+      if(e == hipSuccess) { e = d_seed_off.alloc(count + 1); }
+      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
+      // one piece: the caller's capacities, never more seeds than a read has positions for (a refusal is the call's);
+      // several: an estimate, then what the refusal asks for
+      u64 rm = (pieces == 1 ? std::min(seed_capacity, bytes / min_length) : bytes / (8 * min_length) + count + 1);
+      u64 rh = (pieces == 1 ? hit_capacity : 4 * rm);
+      int piece_rc = GCSA2_OK;
+      for(int attempt = 0; attempt < 2; attempt++)
+      {
+        d_seeds.release(); d_hit_off.release(); d_hits.release();
+        e = d_seeds.alloc(rm);
+        if(e == hipSuccess) { e = d_hit_off.alloc(rm + 1); }
+        if(e == hipSuccess) { e = d_hits.alloc(rh); }
+        if(e != hipSuccess) { break; }
+        piece_rc = gcsa2_capped_seeds_device(ix, d_pat.p, d_off.p, count, min_length, max_length, max_count, hit_max, over, d_seed_off.p, d_seeds.p, rm,
+                                             &piece.m, d_hit_off.p, d_hits.p, rh, &piece.h, stream);
+        if(piece_rc == GCSA2_ERR_BUFFER_TOO_SMALL && pieces > 1 && attempt == 0 && (piece.m > rm || piece.h > rh)) { rm = piece.m; rh = piece.h; continue; }
+        break;
+      }
+      if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); break; }
+      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
+      piece.seed_off.resize(count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
+      e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
+      if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
+      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
+    }
+    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+  });
+  u64 m = 0, h = 0;
+  for(const Piece& piece : done) { m += piece.m; h += piece.h; }
+  *total_seeds = m;
+  *total_hits = h;
+  if(rc != GCSA2_OK) { return rc; }
+  if(m > seed_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed buffer too small"); }
+  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
+  u64 mbase = 0, hbase = 0;
+  for(u64 c = 0; c < pieces; c++)
+  {
+    const Piece& piece = done[c];
+    const u64 b = cut[c], count = cut[c + 1] - b;
+    for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
+    if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
+    for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }
+    if(piece.h > 0) { std::memcpy(hits + hbase, piece.hits.data(), piece.h * sizeof(u64)); }
+    mbase += piece.m;
+    hbase += piece.h;
+  }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_capped_seeds_batch: ") + e.what()); }
 }
 
 }  // extern "C"

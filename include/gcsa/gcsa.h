@@ -319,6 +319,43 @@ public:
     hits.resize(total_hits);
   }
 
+  // Frequency-bounded seeds in one call (gcsa2_capped_seeds_batch): from the end of every read the match is extended until it
+  // has min_length characters and count(range) <= max_count, emitted as {position, length, sp, ep, count}, and the search
+  // starts again behind it; max_length (0: none, a mapper passes order()) cuts an attempt short.  The seeds of a read do not
+  // overlap and come in descending position; their hits follow the rules of mem_hits_batch.  Seeds of read q:
+  // [seed_offsets[q], seed_offsets[q + 1]); hits of seed i: [hit_offsets[i], hit_offsets[i + 1]).  (seed_offsets, seeds) is a MEM
+  // CSR: sub_mem_hits_batch takes it as it is.  Needs no LCP array.
+  void capped_seeds_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type min_length,
+                          size_type max_length, size_type max_count, size_type hit_max, bool sample, std::vector<size_type>& seed_offsets,
+                          std::vector<gcsa2_mem>& seeds, std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    seed_offsets.assign(np + 1, 0);
+    seeds.clear();
+    hits.clear();
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total_seeds = 0, total_hits = 0;
+    for(int attempt = 0; attempt < 2; attempt++)           // the first call sizes the buffers, unless nothing is found
+    {
+      hit_offsets.assign(seeds.size() + 1, 0);
+      const int rc = gcsa2_capped_seeds_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                              min_length, max_length, max_count, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP,
+                                              seed_offsets.data(), seeds.data(), seeds.size(), &total_seeds, hit_offsets.data(), hits.data(),
+                                              hits.size(), &total_hits);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && (total_seeds > seeds.size() || total_hits > hits.size()))
+      {
+        seeds.assign(total_seeds, gcsa2_mem());
+        hits.assign(total_hits, 0);
+        continue;
+      }
+      check(rc, "GCSA::capped_seeds_batch()");
+      break;
+    }
+    seeds.resize(total_seeds);
+    hit_offsets.resize(total_seeds + 1);
+    hits.resize(total_hits);
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).

@@ -725,6 +725,80 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* index, const uint8_t* patterns, con
                           uint64_t k, uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles,
                           uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
                           uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* ---- capped seeds: the shortest matches of every read that occur at most max_count times, with their positions -------------
+ * A frequency-bounded seed (BWA-MEM's third seeding round, LAST's adaptive seeds): where a read crosses a repeat, MEMs and
+ * k-mers end above hit_max and get no positions (GCSA2_MEM_OVER_SKIP) or a sample of them; here the match is extended until it
+ * occurs at most max_count times, emitted, and the search starts again behind it.  No composition of the other calls gives
+ * this: it needs count() of the range after every step.  (d_patterns, d_offsets, n_patterns) are those of gcsa2_find_device;
+ * hit_max and over those of gcsa2_mem_hits_device.  min_length >= 1; max_length: 0 means none, a mapper passes gcsa2_order();
+ * max_count >= 1.
+ *
+ * DEFINITION.  The seeds of read P of length L, over an index of n path nodes, are what this walk emits, in its order:
+ *
+ *   e = L
+ *   while e > 0:
+ *     r = (0, n - 1); i = e; fail = none                    r is the range of P[i .. e)
+ *     loop:
+ *       if i == 0: fail = -1; break                                              (the read's start)
+ *       if max_length != 0 and e - i == max_length: fail = i - 1; break          (cut: the step is not taken)
+ *       r2 = LF(r, char2comp[P[i - 1]])
+ *       if r2 is empty: fail = i - 1; break
+ *       i -= 1; r = r2
+ *       if e - i >= min_length and count(r) <= max_count:
+ *         emit {position = i, length = e - i, sp = r.sp, ep = r.ep, count = count(r)}; break
+ *     e = i if a seed was emitted, else max(0, min(e - 1, fail + 1))
+ *
+ * What follows from it:
+ *   - The seeds of a read do not overlap, and they come in descending position -- the order in which gcsa2_match_breaks_device
+ *     lists its records.
+ *   - count() is evaluated only once the match has min_length characters.
+ *   - A walk takes at most 2 L LF steps: a failed attempt of s steps moves e by at least max(1, s - 1).
+ *   - After a failure the next attempt ends with the character that failed (BWA's skip).  This is greedy on purpose: the
+ *     contract is the walk itself, not "every shortest match under the cap".
+ *   - Only non-empty ranges are emitted, so neither of find()'s empty forms appears.
+ *   - A read shorter than min_length and an index of size 0 give no seed.
+ *   - (sp, ep) of a seed is bit for bit what gcsa2_find_device returns for P[position, position + length); count =
+ *     GCSA::count(sp, ep).  With max_length == 0 a length may exceed gcsa2_order(), with find()'s false positives.
+ *   - The record type is gcsa2_mem, so that a seed CSR is a valid input to gcsa2_sub_mem_hits_device as it is.
+ *
+ * Seeds of read q: d_seeds[d_seed_offsets[q] .. d_seed_offsets[q + 1]) (n_patterns + 1 offsets; the last one is the total).
+ * Hits of seed i: d_hits[d_hit_offsets[i] .. d_hit_offsets[i + 1]) (seed_capacity + 1 offsets), by the rules of
+ * gcsa2_mem_hits_device, word for word: hit_max == 0 (no cap) or count <= hit_max: the sorted distinct values of
+ * gcsa2_locate_into(sort = 1); otherwise GCSA2_MEM_OVER_SKIP: none (the seed and its count are still reported), or
+ * GCSA2_MEM_OVER_SAMPLE: the values of gcsa2_locate_max(range, hit_max), value for value and in order; its INVALID_ARGUMENT for a
+ * range the reference would draw forever on is passed through.  A caller who wants every seed placed passes hit_max = 0 or
+ * hit_max >= max_count.
+ *
+ * *total_seeds and *total_hits are always the sizes needed; if either exceeds its capacity the call fails with
+ * GCSA2_ERR_BUFFER_TOO_SMALL and writes nothing into d_seed_offsets, d_seeds, d_hit_offsets or d_hits.  Nothing is ever written
+ * behind a capacity.  d_seeds / d_hits may be NULL with a capacity of 0 (a sizing call).  GCSA2_ERR_INVALID_ARGUMENT, with
+ * nothing written and before any device is touched: min_length == 0, max_count == 0, max_length != 0 && min_length > max_length,
+ * an unknown `over`, a NULL index or a NULL total pointer.  Needs the samples and the counters (GCSA2_ERR_MISSING_COMPONENT,
+ * likewise); it does NOT need the LCP array -- the first seed finder with positions that works on an image created without one.
+ * 2^32 or more reads or seeds: GCSA2_ERR_BUFFER_TOO_SMALL ("split the batch").  n_patterns == 0 and no seed at all are GCSA2_OK:
+ * the seed offsets are zeroed and d_hit_offsets[0] = 0.  A walk that takes more than 2 L + 2 LF steps (an inconsistent index) fails
+ * with GCSA2_ERR_HIP instead of spinning.  Enqueued on `stream`, complete on return.
+ *
+ * One lane per read, persistent lanes, two passes of the same walk (sizes, a scan, then the records at their slots): device
+ * scratch per call is two words per read, the rest per seed.  The counts the walk computed go to the classify / locate / gather
+ * tail of the MEM hits; count() is not evaluated twice.  Neither the seed table nor the jump table is read.  Where the image has
+ * pair blocks, the steps of an attempt that is still two characters or more short of min_length -- whose ranges and counts the
+ * walk does not look at -- go two per request when both are non-empty, and are replayed one by one when not, so that `fail`
+ * is exact: the results are the same bit for bit with and without pair blocks. */
+int gcsa2_capped_seeds_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                              uint64_t min_length, uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over,
+                              uint64_t* d_seed_offsets,                    /* n_patterns + 1 */
+                              gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                              uint64_t* d_hit_offsets,                     /* seed_capacity + 1 */
+                              uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+/* The same for a batch in host memory: offsets[0] == 0, decreasing offsets are refused (GCSA2_ERR_INVALID_ARGUMENT).  A batch
+ * of two pieces' worth of read bytes or more travels in pieces of whole reads (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS, as the MEM
+ * calls); seeds, hit offsets and hits keep read order across pieces.  On GCSA2_ERR_BUFFER_TOO_SMALL a batch in one piece
+ * writes nothing; one in pieces leaves the result arrays unspecified, as gcsa2_mem_hits_batch.  Complete on return. */
+int gcsa2_capped_seeds_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                             uint64_t min_length, uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over,
+                             uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                             uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
