@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("GCSA2_HIP_LIB") or os.path.join(_HERE, "lib", "libgcs
 
 STATUS_BUFFER_TOO_SMALL = -6
 KMER_COUNTS = 1     # GCSA2_KMER_COUNTS
+SUPPORT_PER_BIN = 1     # GCSA2_SUPPORT_PER_BIN
+SUPPORT_STATS = ("windows", "found", "counted", "distinct", "values", "added", "dropped")     # gcsa2_support_stats
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -45,6 +47,7 @@ EXPORTS = [
     "gcsa2_extend_device", "gcsa2_extend_batch", "gcsa2_kmer_windows_device", "gcsa2_kmer_windows_batch",
     "gcsa2_kmer_hits_device", "gcsa2_kmer_hits_batch",
     "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
+    "gcsa2_kmer_support_device", "gcsa2_kmer_support_batch", "gcsa2_seed_support_device",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -168,6 +171,9 @@ def load_library():
     L.gcsa2_kmer_windows_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, C.c_int, vp, vp, vp, vp, u64, u64p]
     L.gcsa2_kmer_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_kmer_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_kmer_support_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp, vp]
+    L.gcsa2_kmer_support_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp]
+    L.gcsa2_seed_support_device.argtypes = [vp, vp, u64, vp, u64, u64, C.c_int, vp, u64, vp, vp]
     L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -643,6 +649,50 @@ class GCSA:
             err.needed = (total_m.value, total_h.value)
             raise err
         return total_m.value, total_h.value
+
+    def kmer_support_batch(self, patterns, offsets, k, stride=1, hit_max=0, shift=11, n_bins=None, per_bin=False, support=None):
+        """Read k-mers summed per graph node (gcsa2_kmer_support_batch): (support, stats).  Every window P_q[j stride, j stride +
+        k) with a non-empty find() and hit_max == 0 or count() <= hit_max adds 1 to support[v >> shift] for every located value
+        v of its range (per_bin: once per distinct bin); shift = 11 gives node ids, 0 exact positions.  Needs n_bins (a fresh
+        zeroed array) or `support`, a uint64 array that is added into.  Contributions to bins >= n_bins are counted in
+        stats["dropped"].  stats: a dict of SUPPORT_STATS."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        if support is None:
+            if n_bins is None:
+                raise ValueError("kmer_support_batch needs n_bins or a support array to add into")
+            support = np.zeros(int(n_bins), dtype=np.uint64)
+        else:
+            assert support.dtype == np.uint64 and support.ndim == 1 and support.flags.c_contiguous
+            if n_bins is not None and int(n_bins) != support.shape[0]:
+                raise ValueError("n_bins differs from the length of the support array")
+        stats = (C.c_uint64 * len(SUPPORT_STATS))()
+        _check(self._L.gcsa2_kmer_support_batch(self._h, _p8(patterns), _p64(offsets), n, int(k), int(stride), int(hit_max), int(shift),
+                                                SUPPORT_PER_BIN if per_bin else 0, support.ctypes.data if support.shape[0] else None,
+                                                support.shape[0], stats))
+        return support, dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
+
+    def kmer_support_device(self, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_support, n_bins, stream=0):
+        """gcsa2_kmer_support_device on caller-owned device buffers (raw pointers): d_support n_bins u64 that are added into
+        (0 / None with n_bins == 0: a statistics run).  Complete on return.  Returns the stats as a dict of SUPPORT_STATS."""
+        stats = (C.c_uint64 * len(SUPPORT_STATS))()
+        rc = self._L.gcsa2_kmer_support_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), int(shift),
+                                               int(flags), d_support or None, int(n_bins), stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
+
+    def seed_support_device(self, d_seeds, n_seeds, d_weights, hit_max, shift, flags, d_support, n_bins, stream=0):
+        """gcsa2_seed_support_device on caller-owned device buffers (raw pointers): d_seeds n_seeds records of five u64 (only sp
+        and ep are read), d_weights n_seeds u64 or 0 / None (1 each), d_support n_bins u64 that are added into.  Complete on
+        return.  Returns the stats as a dict of SUPPORT_STATS."""
+        stats = (C.c_uint64 * len(SUPPORT_STATS))()
+        rc = self._L.gcsa2_seed_support_device(self._h, d_seeds or None, int(n_seeds), d_weights or None, int(hit_max), int(shift), int(flags),
+                                               d_support or None, int(n_bins), stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
 
     def lf_node_batch(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)

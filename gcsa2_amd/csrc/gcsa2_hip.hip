@@ -20,6 +20,8 @@
 //                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
 //   kernels_seeds.hpp   k_capped_seeds        GCSA::LF(range, comp) + GCSA::count per step: the shortest matches under an occurrence cap
 //                                                                        include/gcsa/gcsa.h:155-162, src/gcsa.cpp:802-809
+//   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
+//                                                                        src/gcsa.cpp:827-842
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
 #include "sdsl_reader.hpp"
@@ -56,6 +58,7 @@ using namespace g2;
 #include "kernels_lcp.hpp"
 #include "kernels_submem.hpp"
 #include "kernels_seeds.hpp"
+#include "kernels_support.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -5728,6 +5731,327 @@ int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_capped_seeds_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== k-mer support: read k-mers (or any seed records) summed per graph node (kernels_support.hpp) ==========================
+namespace {
+
+constexpr u64 SUPPORT_CHUNK_DEFAULT = u64(1) << 22;    // values (before deduplication) located per chunk: the smallest budget within 2.5 % of the best time, profiles/kmer_support.md
+
+// GCSA2_SUPPORT_CHUNK (a test knob, read per call): the value budget of a chunk.  The result never depends on it.
+u64 support_chunk_budget()
+{
+  u64 budget = SUPPORT_CHUNK_DEFAULT;
+  const char* env = std::getenv("GCSA2_SUPPORT_CHUNK");
+  if(env != nullptr && *env != 0)
+  {
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(env, &end, 10);
+    if(end != env && *end == 0 && v >= 1) { budget = v; }
+  }
+  return std::min(budget, (u64(1) << 31) - 1);       // one pass of the locate pipeline
+}
+
+// what every form refuses before any device is touched, then the components the call needs (no LCP array)
+int support_checks(const gcsa2_index* ix, u64 shift, int flags, const void* support, u64 n_bins, const char* support_name)
+{
+  CHECK_INDEX(ix);
+  if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "support: shift must be below 64"); }
+  if((flags & ~GCSA2_SUPPORT_PER_BIN) != 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "support: unknown flags (GCSA2_SUPPORT_PER_BIN)"); }
+  if(support == nullptr && n_bins > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string("support: ") + support_name + " is NULL with n_bins > 0"); }
+  return locate_checks(ix, 0);
+}
+
+int kmer_support_checks(const gcsa2_index* ix, u64 k, u64 stride, u64 shift, int flags, const void* support, u64 n_bins, const char* support_name)
+{
+  CHECK_INDEX(ix);
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: k must be at least 1"); }
+  if(stride == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: stride must be at least 1"); }
+  return support_checks(ix, shift, flags, support, n_bins, support_name);
+}
+
+// Steps 2 onward of a support call: m (1 <= m < 2^32) records of `words` u64 with (sp, ep) at words 2 and 3, their count()s
+// in `known` or (nullptr) computed here, weights or (nullptr) 1 each, are added to d_support.  Fills every field of *st_out
+// but `windows`.  Host round trips: the number of counted records, the number of distinct ranges, one per chunk for its cut,
+// those of every chunk's locate pass, the end.  Scratch: per counted record 50 bytes and the sorts' temporaries; per distinct
+// range 32 bytes; per chunk -- the same buffers for every chunk -- 8 bytes per range and 8 1/8 bytes per value of the largest.
+int support_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* known, const u64* weights, u64 m, u64 hit_max, u64 shift, int flags,
+                 u64* d_support, u64 n_bins, gcsa2_support_stats* st_out, Scratch& scratch, hipStream_t st)
+{
+  // 1. the cap first: only the counted records reach the sort
+  unsigned long long* stat = nullptr;
+  u64 *csp = nullptr, *cep = nullptr, *ccnt = nullptr, *cw = nullptr;
+  HIP_TRY(scratch.get(stat, SUP_WORDS));
+  HIP_TRY(scratch.get(csp, m)); HIP_TRY(scratch.get(cep, m)); HIP_TRY(scratch.get(ccnt, m));
+  if(weights != nullptr) { HIP_TRY(scratch.get(cw, m)); }
+  HIP_TRY(hipMemsetAsync(stat, 0, SUP_WORDS * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_support_class, dim3(unsigned((m + SUPPORT_CLASS_TPB - 1) / SUPPORT_CLASS_TPB)), dim3(SUPPORT_CLASS_TPB), 0, st, ix->img, recs, words, known, weights, m, hit_max, stat, csp, cep, ccnt, cw);
+  LAUNCH_CHECK("k_support_class");
+  unsigned long long host_stat[SUP_WORDS];
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const u64 c = host_stat[SUP_CURSOR] & 0xFFFFFFFFull;
+  st_out->found = host_stat[SUP_CURSOR] >> 32;
+  st_out->counted = c;
+  if(c == 0) { scratch.settled = true; return GCSA2_OK; }
+  // 2. equal ranges fold: stable radix passes by ep, then by sp, over as many bits as a path node has
+  u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
+  int bits = 1;
+  while(bits < 64 && (top >> bits) != 0) { bits++; }
+  u64 *key_a = nullptr, *key_b = nullptr, *ranges = nullptr, *run_counts = nullptr, *run_off = nullptr;
+  u32 *perm_a = nullptr, *perm_b = nullptr, *head = nullptr, *run = nullptr;
+  unsigned long long* mult = nullptr;
+  char* tmp = nullptr;
+  HIP_TRY(scratch.get(key_a, c)); HIP_TRY(scratch.get(key_b, c));
+  HIP_TRY(scratch.get(perm_a, c)); HIP_TRY(scratch.get(perm_b, c));
+  HIP_TRY(scratch.get(head, c)); HIP_TRY(scratch.get(run, c));
+  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, head, run, size_t(c), st));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, key_a, key_b, size_t(c + 1), st));
+  HIP_TRY(scratch.get(tmp, std::max(sort_bytes, std::max(scan_bytes, sum_bytes))));
+  hipLaunchKernelGGL(k_support_iota, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, c);
+  LAUNCH_CHECK("k_support_iota");
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));      // perm_b: by ep
+  hipLaunchKernelGGL(k_support_gather, dim3(grid_for(c)), dim3(TPB), 0, st, csp, perm_b, c, key_a);
+  LAUNCH_CHECK("k_support_gather");
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, perm_b, perm_a, size_t(c), 0, bits, st));    // key_b, perm_a: by (sp, ep)
+  hipLaunchKernelGGL(k_support_heads, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, perm_a, c, head);
+  LAUNCH_CHECK("k_support_heads");
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, scan_bytes, head, run, size_t(c), st));
+  u32 d32 = 0;
+  HIP_TRY(hipMemcpyAsync(&d32, run + (c - 1), sizeof(u32), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const u64 d = d32;
+  st_out->distinct = d;
+  HIP_TRY(scratch.get(ranges, 2 * d)); HIP_TRY(scratch.get(run_counts, d + 1)); HIP_TRY(scratch.get(run_off, d + 1)); HIP_TRY(scratch.get(mult, d));
+  HIP_TRY(hipMemsetAsync(mult, 0, d * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(run_counts + d, 0, sizeof(u64), st));
+  hipLaunchKernelGGL(k_support_runs, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, ccnt, cw, perm_a, run, c, ranges, run_counts, mult);
+  LAUNCH_CHECK("k_support_runs");
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, sum_bytes, run_counts, run_off, size_t(d + 1), st));
+  // 3. the chunks: runs q0 .. q1 - 1 whose count() sum stays within the budget, one run at least
+  const u64 budget = support_chunk_budget();
+  struct Chunk { u64 q0, q1, raw; };
+  std::vector<Chunk> chunks;
+  unsigned long long* d_cut = stat + SUP_CUT;
+  u64 most_runs = 0, most_raw = 0;
+  for(u64 q0 = 0; q0 < d; )
+  {
+    unsigned long long cut[2] = {0, 0};
+    hipLaunchKernelGGL(k_support_cut, dim3(1), dim3(1), 0, st, run_off, d, q0, budget, ix->tune.locate_split_queries, d_cut);
+    LAUNCH_CHECK("k_support_cut");
+    HIP_TRY(hipMemcpyAsync(cut, d_cut, sizeof(cut), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const u64 q1 = cut[0], raw = cut[1];
+    if(q1 <= q0 || q1 > d) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "support: a chunk without a range"); }
+    chunks.push_back(Chunk{q0, q1, raw});
+    most_runs = std::max(most_runs, q1 - q0); most_raw = std::max(most_raw, raw);
+    q0 = q1;
+  }
+  // 4. locate and add, chunk by chunk, in the same scratch
+  u64 *off = nullptr, *val = nullptr, *owners = nullptr;
+  HIP_TRY(scratch.get(off, most_runs + 1)); HIP_TRY(scratch.get(val, most_raw)); HIP_TRY(scratch.get(owners, most_raw / OWNER_SPAN + 3));
+  u64 values = 0;
+  for(const Chunk& chunk : chunks)
+  {
+    const u64 runs = chunk.q1 - chunk.q0;
+    u64 total = 0;
+    ValuesProvider provide = [val, most_raw](u64 count) -> u64* { return count <= most_raw ? val : nullptr; };
+    const int rc = locate_core(ix, ranges + 2 * chunk.q0, runs, 1, off, provide, &total, st, val, most_raw);
+    if(rc != GCSA2_OK) { return rc; }
+    values += total;
+    if(total == 0) { continue; }
+    const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, off, runs, total, OWNER_SPAN, spans, owners);
+    LAUNCH_CHECK("k_block_owners");
+    hipLaunchKernelGGL(k_support_add, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, runs, total, mult + chunk.q0, u32(shift),
+                       int((flags & GCSA2_SUPPORT_PER_BIN) != 0), reinterpret_cast<unsigned long long*>(d_support), n_bins, stat);
+    LAUNCH_CHECK("k_support_add");
+    scratch.settled = false;
+  }
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  st_out->values = values;
+  st_out->added = host_stat[SUP_ADDED];
+  st_out->dropped = host_stat[SUP_DROPPED];
+  return GCSA2_OK;
+}
+
+// gcsa2_kmer_support_device after its argument checks (0 < n_patterns < 2^32): the search of gcsa2_kmer_hits_device with room
+// for every window, so that it runs once; its records stay in arrival order and go to support_tail with their count()s.
+int kmer_support_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max,
+                      u64 shift, int flags, u64* d_support, u64 n_bins, gcsa2_support_stats* st_out, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *sizes = nullptr, *woff = nullptr;
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  HIP_TRY(scratch.get(woff, n_patterns + 1));
+  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
+  LAUNCH_CHECK("k_window_counts");
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  u64 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more windows in one call; split the batch"); }
+  st_out->windows = total;
+  if(total == 0) { return GCSA2_OK; }
+  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
+  u64* owners = nullptr;
+  SeedEmit emit{};
+  HIP_TRY(scratch.get(owners, spans + 1));
+  HIP_TRY(scratch.get(emit.cursor, 1));
+  HIP_TRY(scratch.get(emit.base, spans));
+  HIP_TRY(scratch.get(emit.found, spans + 1));
+  HIP_TRY(scratch.get(emit.mask, spans));
+  emit.capacity = total;
+  HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
+  HIP_TRY(scratch.get(emit.counts, emit.capacity));
+  scratch.settled = false;
+  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
+  LAUNCH_CHECK("k_block_owners");
+  HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
+  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
+  gcsa2_kmer_profile* const no_profiles = nullptr;
+  if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
+  else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
+  LAUNCH_CHECK("k_kmer_seeds");
+  u64 m = 0;
+  HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if(m > emit.capacity) { return fail(GCSA2_ERR_HIP, "kmer_support: more seeds than windows"); }
+  if(m == 0) { return GCSA2_OK; }
+  scratch.settled = false;
+  return support_tail(ix, emit.recs, 4, emit.counts, nullptr, m, hit_max, shift, flags, d_support, n_bins, st_out, scratch, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_support_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                              uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, uint64_t* d_support, uint64_t n_bins,
+                              gcsa2_support_stats* stats, void* stream)
+{
+  int rc = kmer_support_checks(ix, k, stride, shift, flags, d_support, n_bins, "d_support");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_support_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  rc = kmer_support_core(ix, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_support, n_bins, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_support_device: ") + e.what()); }
+}
+
+int gcsa2_seed_support_device(const gcsa2_index* ix, const gcsa2_mem* d_seeds, uint64_t n_seeds, const uint64_t* d_weights, uint64_t hit_max,
+                              uint64_t shift, int flags, uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream)
+{
+  int rc = support_checks(ix, shift, flags, d_support, n_bins, "d_support");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_support: d_seeds is NULL"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_support: 2^32 or more seeds in one call; split the batch"); }
+  gcsa2_support_stats sums{};
+  sums.windows = n_seeds;
+  if(n_seeds == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  {
+    Scratch scratch(ix, st);
+    rc = support_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, hit_max, shift, flags, d_support, n_bins, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_support_device: ") + e.what()); }
+}
+
+// The host form.  One zeroed device array of n_bins for the whole call; the reads travel in pieces of whole reads
+// (tune.ms_piece_bytes, cut_pieces) on tune.ms_threads host threads, each piece one gcsa2_kmer_support_device on its thread's
+// stream -- the pieces add into the one array with atomics -- and the array is added into the caller's at the end.
+int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                             uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, uint64_t* support, uint64_t n_bins,
+                             gcsa2_support_stats* stats)
+{
+  int rc = kmer_support_checks(ix, k, stride, shift, flags, support, n_bins, "support");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_support_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: offsets is NULL"); }
+  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: patterns is NULL"); }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  u64 windows_all = 0;
+  for(u64 q = 0; q < n_patterns; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    if(len >= k) { windows_all += (len - k) / stride + 1; }
+  }
+  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more windows in one call; split the batch"); }
+  DeviceGuard guard(ix->device);
+  DBuf<u64> d_sup;
+  HIP_TRY(d_sup.alloc(n_bins));
+  HIP_TRY(hipMemset(d_sup.p, 0, (n_bins > 0 ? n_bins : 1) * sizeof(u64)));
+  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
+                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
+  const u64 pieces = cut.size() - 1;
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  std::vector<gcsa2_support_stats> done(pieces);
+  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard piece_guard(ix->device);
+    std::vector<u64> local;
+    hipStream_t stream = nullptr;
+    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      DBuf<u8> d_pat; DBuf<u64> d_off;
+      hipError_t e = d_pat.alloc(bytes + 16);
+      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
+      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
+      const int piece_rc = gcsa2_kmer_support_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_sup.p, n_bins, &done[c], stream);
+      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
+    }
+    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  for(const gcsa2_support_stats& s : done)
+  {
+    sums.windows += s.windows; sums.found += s.found; sums.counted += s.counted; sums.distinct += s.distinct;
+    sums.values += s.values; sums.added += s.added; sums.dropped += s.dropped;
+  }
+  if(n_bins > 0)
+  {
+    std::vector<u64> got(n_bins);
+    HIP_TRY(hipMemcpy(got.data(), d_sup.p, n_bins * sizeof(u64), hipMemcpyDeviceToHost));
+    for(u64 i = 0; i < n_bins; i++) { support[i] += got[i]; }
+  }
+  if(stats != nullptr) { *stats = sums; }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_support_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -356,6 +356,23 @@ public:
     hits.resize(total_hits);
   }
 
+  // A genotyper's or a coverage screen's lookup in one call (gcsa2_kmer_support_batch): every window P_q[j stride, j stride + k)
+  // with a non-empty find() and hit_max == 0 or count(range) <= hit_max adds 1 to support[v >> shift] for every located value v
+  // of its range (per_bin: once per distinct bin).  shift = 11 (Node::ID_OFFSET) gives node ids.  ADDS into `support`, whose
+  // size is the number of bins: contributions beyond it are counted in stats->dropped.  Needs no LCP array.
+  void kmer_support_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type stride,
+                          size_type hit_max, size_type shift, bool per_bin, std::vector<size_type>& support,
+                          gcsa2_support_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    const int rc = gcsa2_kmer_support_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                            k, stride, hit_max, shift, per_bin ? GCSA2_SUPPORT_PER_BIN : 0,
+                                            support.empty() ? nullptr : support.data(), support.size(), stats);
+    check(rc, "GCSA::kmer_support_batch()");
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).

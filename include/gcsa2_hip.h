@@ -799,6 +799,65 @@ int gcsa2_capped_seeds_batch(const gcsa2_index* index, const uint8_t* patterns, 
                              uint64_t min_length, uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over,
                              uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
                              uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* ---- k-mer support: the k-mers of every read (or any seed records), summed per graph node -----------------------------------
+ * The call of the second caller named under k-mer windows and k-mer hits: a k-mer genotyper or a coverage screen wants no seed
+ * lists but, per graph node, how many read k-mers landed on it, summed over all reads.  With gcsa2_kmer_hits_batch it would
+ * pull every hit of every window across the link and bin them itself; here find, count, locate and the binning stay on the
+ * device, every distinct range of a call is located ONCE however many reads carry its k-mer, and what leaves the device is one
+ * counter per bin.  (d_patterns, d_offsets, n_patterns), k and stride are those of gcsa2_kmer_windows_device.
+ *
+ * DEFINITION.
+ *   - The windows are exactly those of gcsa2_kmer_windows_device for (k, stride).  A window is FOUND if its find() range is
+ *     non-empty.
+ *   - A found window is COUNTED if hit_max == 0 or count(range) <= hit_max: the GCSA2_MEM_OVER_SKIP rule of the MEM hits.  There
+ *     is no sampling policy here: a random sample has no place in a sum.  (A seed record whose range reaches beyond the index
+ *     has count() == 0, GCSA::count's answer, and is not counted: there is nothing to locate.)
+ *   - A counted window of weight w (1 for k-mer windows) adds w to d_support[v >> shift] for every value v of
+ *     gcsa2_locate_into(range, sort = 1), the sorted distinct values.  With GCSA2_SUPPORT_PER_BIN it adds w once per distinct
+ *     v >> shift among those values.
+ *   - shift = 11 (Node::ID_OFFSET) gives node ids, shift = 0 exact positions.
+ *   - A contribution whose bin is >= n_bins is not written anywhere; its weight goes to stats.dropped.
+ *   - The call ADDS and never zeroes: support accumulates over calls, and the caller clears it.
+ *   - stats (host, may be NULL): windows and found as in the profiles of gcsa2_kmer_windows_device, summed over the reads;
+ *     counted as above; distinct = the number of distinct (sp, ep) among the counted windows; values = the sum over those
+ *     distinct ranges of the number of their distinct located values; added = the total weight added to d_support; dropped as
+ *     above.  Without GCSA2_SUPPORT_PER_BIN and with weights 1, added + dropped is the sum over the counted windows of
+ *     |locate(range)|.
+ *
+ * GCSA2_ERR_INVALID_ARGUMENT, with nothing written (stats included) and before any device is touched: a NULL index, k == 0,
+ * stride == 0, shift >= 64, an unknown flag, d_support == NULL with n_bins > 0.  n_bins == 0 is valid: everything is dropped, a
+ * statistics run.  Needs the samples and the counters (GCSA2_ERR_MISSING_COMPONENT, likewise), not the LCP array.  2^32 or more
+ * reads, windows or seeds: GCSA2_ERR_BUFFER_TOO_SMALL ("split the batch"), as gcsa2_kmer_hits_device.  n_patterns == 0, no window
+ * and nothing found are GCSA2_OK with zero stats (but `windows`).  The sum is NOT transactional: on an error after work has begun
+ * d_support may hold a partial sum, and stats is not written.  Enqueued on `stream`, complete on return.
+ *
+ * The search is that of gcsa2_kmer_hits_device; its records stay in arrival order -- no window order, no seed offsets, no
+ * profiles.  The cap is applied first, the counted records are sorted by (sp, ep), runs become {range, multiplicity}, and the
+ * distinct ranges are located in chunks whose count() sum stays within a value budget (a chunk always holds one range at
+ * least), so that device scratch does not grow with the call's total hits; every chunk's values are added with 64-bit vector
+ * atomics, neighbouring lanes of one bin as one add.  GCSA2_SUPPORT_CHUNK (values, read per call; default 2^22, the smallest
+ * budget within 2.5 % of the best time measured, profiles/kmer_support.md) is a test knob: no result depends on it. */
+typedef struct gcsa2_support_stats { uint64_t windows, found, counted, distinct, values, added, dropped; } gcsa2_support_stats;
+#define GCSA2_SUPPORT_PER_BIN 1   /* a window adds to a bin once, however many of its positions fall into it */
+int gcsa2_kmer_support_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                              uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                              uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats /* host, may be NULL */, void* stream);
+/* The same for reads in host memory, into a host array: offsets[0] == 0, decreasing offsets are refused
+ * (GCSA2_ERR_INVALID_ARGUMENT).  A batch of two pieces' worth of read bytes or more travels in pieces of whole reads
+ * (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS, as the MEM calls).  One zeroed device array of n_bins serves the whole call and is added
+ * into `support` at the end (on an error `support` is untouched).  stats are summed over the pieces: distinct and values are then
+ * per-piece sums, an upper bound of the whole-batch figures; everything else is exact.  Complete on return. */
+int gcsa2_kmer_support_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                             uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                             uint64_t* support /* host, n_bins */, uint64_t n_bins, gcsa2_support_stats* stats);
+/* The same sum over seed records the caller already has on the device -- MEMs, sub-MEMs, k-mer or capped seeds, as the other
+ * calls emit them -- with a weight per record (d_weights, n_seeds entries, or NULL = 1 each; 0 is allowed).  Only sp and ep of a
+ * record are read: count() is evaluated again and the record's count field is ignored.  A record with an empty range (either
+ * form) contributes nothing.  stats.windows = n_seeds, stats.found = the records with a non-empty range; a run's multiplicity
+ * is the sum of its records' weights.  n_seeds == 0 is GCSA2_OK.  Refusals, limits and everything else as above. */
+int gcsa2_seed_support_device(const gcsa2_index* index, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                              const uint64_t* d_weights /* or NULL = 1 each */, uint64_t hit_max, uint64_t shift, int flags,
+                              uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
