@@ -1790,7 +1790,9 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
   // operations too, so every wait for the LDS behind a prefetch waited for the prefetch.  Said to be global memory here.)
   typedef const __attribute__((address_space(1))) u64* global_values;
   const global_values src = (global_values)(over_src[blockIdx.x] != nullptr ? over_src[blockIdx.x] : values + b);
-  constexpr u64 KEEP = ~LOCATE_DIRECT;                        // (a raw value has the bit clear: k_build_locate_table)
+  // (the flag is cleared only in what comes from the table -- a fused range's path nodes have direct entries, k_classify_fused;
+  // a raw value is a whole node_type, and from 63 bits of samples on its bit 63 is a bit of the value)
+  const u64 keep = (over_src[blockIdx.x] != nullptr ? ~LOCATE_DIRECT : ~u64(0));
   if(tid == 0) { s_lo = ~0ull; s_hi = 0; }
   for(u32 k = tid; k < SPLIT_BUCKETS; k += SPLIT_THREADS) { cursor[k] = 0; }
   __syncthreads();
@@ -1803,7 +1805,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
   {
     u64 got[SPLIT_AHEAD];
 #pragma unroll
-    for(u32 j = 0; j < SPLIT_AHEAD; j++) { const u64 i = i0 + u64(j) * SPLIT_THREADS; got[j] = (i < len ? src[i] : src[tid % len]) & KEEP; }
+    for(u32 j = 0; j < SPLIT_AHEAD; j++) { const u64 i = i0 + u64(j) * SPLIT_THREADS; got[j] = (i < len ? src[i] : src[tid % len]) & keep; }
 #pragma unroll
     for(u32 j = 0; j < SPLIT_AHEAD; j++) { lo = (got[j] < lo ? got[j] : lo); hi = (got[j] > hi ? got[j] : hi); }
   }
@@ -1840,7 +1842,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
     {
       u64 got[SPLIT_AHEAD];
 #pragma unroll
-      for(u32 j = 0; j < SPLIT_AHEAD; j++) { got[j] = ahead[j] & KEEP; asm volatile("" : "+v"(got[j])); }
+      for(u32 j = 0; j < SPLIT_AHEAD; j++) { got[j] = ahead[j] & keep; asm volatile("" : "+v"(got[j])); }
 #pragma unroll
       for(u32 j = 0; j < SPLIT_AHEAD; j++) { const u64 i = i0 + u64(SPLIT_AHEAD + j) * SPLIT_THREADS; ahead[j] = src[i < len ? i : len - 1]; }
 #pragma unroll
@@ -1923,7 +1925,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(8
       u32 where[SPLIT_TILE_PER];                              // bucket | rank inside the bucket's values of this tile << 16 (one register: the kernel has 64)
       static_assert(SPLIT_TILED_BUCKETS <= 65536 && SPLIT_TILE <= 65536, "two 16-bit halves");
 #pragma unroll
-      for(u32 j = 0; j < SPLIT_TILE_PER; j++) { got[j] = next[j] & KEEP; asm volatile("" : "+v"(got[j])); }
+      for(u32 j = 0; j < SPLIT_TILE_PER; j++) { got[j] = next[j] & keep; asm volatile("" : "+v"(got[j])); }
       // The next tile's values travel while this one is worked on.  They did not until late in round 6: (i) the loads were
       // flat_load (above); (ii) they sat behind `if(i < len)` branches, and the compiler cannot count memory operations across a
       // branch, so its wait for the PREVIOUS tile's values -- placed at their first use, behind these loads -- was

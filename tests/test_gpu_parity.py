@@ -1582,12 +1582,14 @@ def test_locate_segment_sizes(engine, values):
                                    {"GCSA2_LOCATE_FUSED_COMPACT": "0"}, {"values": "across 2^32"}, {"values": "across 2^32", "GCSA2_SPLIT_TARGET": "24"},
                                    {"values": "across 2^32", "GCSA2_SPLIT_TARGET": "1500", "GCSA2_SPLIT_SKEW": "3000"},
                                    {"GCSA2_LOCATE_FUSE": "0"}, {"GCSA2_LOCATE_IN_PLACE": "0"}, {"GCSA2_LOCATE_FUSE_ABOVE": "600"},
-                                   {"GCSA2_LOCATE_FUSE_ABOVE": "2", "GCSA2_SPLIT_TARGET": "24"}, {"values": "across 2^32", "GCSA2_LOCATE_FUSE_ABOVE": "600", "GCSA2_SPLIT_SKEW": "16"}],
+                                   {"GCSA2_LOCATE_FUSE_ABOVE": "2", "GCSA2_SPLIT_TARGET": "24"}, {"values": "across 2^32", "GCSA2_LOCATE_FUSE_ABOVE": "600", "GCSA2_SPLIT_SKEW": "16"},
+                                   {"values": "across 2^63"}, {"values": "across 2^63", "GCSA2_SPLIT_SKEW": "16"}],
                          ids=["split-with-listed-buckets", "split-with-runs", "split-with-listed-and-skewed-buckets", "split-with-skewed-buckets",
                               "four-kernel-compaction",
                               "64-bit-keys", "64-bit-keys-runs", "64-bit-keys-large-buckets",
                               "table-pass-for-every-range", "sorts-in-scratch", "fused-from-600-nodes",
-                              "fused-from-3-nodes-runs", "fused-64-bit-keys-skewed"])
+                              "fused-from-3-nodes-runs", "fused-64-bit-keys-skewed",
+                              "values-across-2^63", "values-across-2^63-skewed-buckets"])
 def test_locate_many_large_distinct_segments(engine, knobs, monkeypatch):
     """Ranges of thousands of path nodes whose values are all DISTINCT (a linear text: one value per path node), as found
     16-mers of interspersed repeats have on the 2^30-base text of bench.py: dozens of segments beyond the 8192 distinct values
@@ -1613,7 +1615,9 @@ def test_locate_many_large_distinct_segments(engine, knobs, monkeypatch):
     if across:
         # node_type values on both sides of 2^32: the register sorts take 32-bit keys only when a segment's values share their
         # upper halves (sort_segment_regs), the run sort of k_over_split when a run lies within 2^32 of its base
-        g.value += np.uint64((1 << 32) - int(g.value.max()) // 2)
+        # ("across 2^63": bit 63 is the flag of a direct locate-table entry and nothing is fused -- every segment is split from its raw
+        # values, and a skewed bucket goes to the library's segmented sort; tests/test_locate_wide_values.py has the other widths)
+        g.value += np.uint64((1 << int(across.rsplit("^", 1)[1])) - int(g.value.max()) // 2)
     ix = builder.build(g, 16, sample_period=32)
     gpu, lcp = engine.open_index(ix)
     cpu = OracleIndex(ix)
