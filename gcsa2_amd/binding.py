@@ -21,6 +21,12 @@ STATUS_BUFFER_TOO_SMALL = -6
 KMER_COUNTS = 1     # GCSA2_KMER_COUNTS
 SUPPORT_PER_BIN = 1     # GCSA2_SUPPORT_PER_BIN
 SUPPORT_STATS = ("windows", "found", "counted", "distinct", "values", "added", "dropped")     # gcsa2_support_stats
+CLASS_NONE = 0xFFFFFFFF     # GCSA2_CLASS_NONE
+CLASS_LIMIT = 4096          # GCSA2_CLASS_LIMIT
+CLASS_PER_WINDOW = 1        # GCSA2_CLASS_PER_WINDOW
+CLASS_UNAMBIGUOUS = 2       # GCSA2_CLASS_UNAMBIGUOUS
+CLASS_CALL = ("best", "best_votes", "second", "second_votes", "total", "counted")     # gcsa2_class_call
+CLASS_STATS = ("windows", "found", "counted", "distinct", "values", "votes", "unclassified", "ambiguous")     # gcsa2_class_stats
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -48,6 +54,7 @@ EXPORTS = [
     "gcsa2_kmer_hits_device", "gcsa2_kmer_hits_batch",
     "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
     "gcsa2_kmer_support_device", "gcsa2_kmer_support_batch", "gcsa2_seed_support_device",
+    "gcsa2_kmer_classes_device", "gcsa2_kmer_classes_batch", "gcsa2_seed_classes_device",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -174,6 +181,9 @@ def load_library():
     L.gcsa2_kmer_support_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp, vp]
     L.gcsa2_kmer_support_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp]
     L.gcsa2_seed_support_device.argtypes = [vp, vp, u64, vp, u64, u64, C.c_int, vp, u64, vp, vp]
+    L.gcsa2_kmer_classes_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_kmer_classes_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp]
+    L.gcsa2_seed_classes_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
     L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -693,6 +703,52 @@ class GCSA:
         if rc != 0:
             raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
         return dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
+
+    def kmer_classes_batch(self, patterns, offsets, k, class_of_bin, n_classes, stride=1, hit_max=0, shift=11, per_window=False,
+                           unambiguous=False, votes=True, calls=True):
+        """Per read, the votes of its k-mers over classes of graph nodes (gcsa2_kmer_classes_batch): (votes, calls, stats).
+        Every window P_q[j stride, j stride + k) with a non-empty find() and hit_max == 0 or count() <= hit_max votes for the
+        class class_of_bin[v >> shift] of every located value v of its range (a uint32 array; CLASS_NONE, an id >= n_classes
+        or a bin beyond the array: no class): n_c votes for class c, once per class with per_window, and only when all its
+        values share one class with unambiguous.  votes: (reads, n_classes) uint64, written, not added to; calls: (reads, 6)
+        uint64 with the columns CLASS_CALL; either is None when not asked for.  stats: a dict of CLASS_STATS."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        class_of_bin = np.ascontiguousarray(class_of_bin, dtype=np.uint32)
+        n = max(offsets.shape[0], 1) - 1
+        out_votes = np.zeros((n, int(n_classes)), dtype=np.uint64) if votes else None
+        out_calls = np.zeros((n, len(CLASS_CALL)), dtype=np.uint64) if calls else None
+        stats = (C.c_uint64 * len(CLASS_STATS))()
+        flags = (CLASS_PER_WINDOW if per_window else 0) | (CLASS_UNAMBIGUOUS if unambiguous else 0)
+        _check(self._L.gcsa2_kmer_classes_batch(self._h, _p8(patterns), _p64(offsets), n, int(k), int(stride), int(hit_max), int(shift), flags,
+                                                class_of_bin.ctypes.data if class_of_bin.shape[0] else None, class_of_bin.shape[0], int(n_classes),
+                                                out_votes.ctypes.data if votes else None, out_calls.ctypes.data if calls else None, stats))
+        return out_votes, out_calls, dict(zip(CLASS_STATS, (int(x) for x in stats)))
+
+    def kmer_classes_device(self, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_class_of_bin, n_bins, n_classes,
+                            d_votes, d_calls, stream=0, want_stats=True):
+        """gcsa2_kmer_classes_device on caller-owned device buffers (raw pointers): d_class_of_bin n_bins u32, d_votes n_patterns x
+        n_classes u64 and d_calls n_patterns records of six u64, both written (0 / None: not wanted).  Complete on return.
+        Returns the stats as a dict of CLASS_STATS, or None with want_stats=False (a NULL stats pointer)."""
+        stats = (C.c_uint64 * len(CLASS_STATS))() if want_stats else None
+        rc = self._L.gcsa2_kmer_classes_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), int(shift), int(flags),
+                                               d_class_of_bin or None, int(n_bins), int(n_classes), d_votes or None, d_calls or None, stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None
+
+    def seed_classes_device(self, d_group_offsets, n_groups, d_seeds, n_seeds, d_weights, hit_max, shift, flags, d_class_of_bin, n_bins,
+                            n_classes, d_votes, d_calls, stream=0, want_stats=True):
+        """gcsa2_seed_classes_device on caller-owned device buffers (raw pointers): group g owns the records
+        [d_group_offsets[g], d_group_offsets[g + 1]) of d_seeds (five u64 each, only sp and ep are read), d_weights n_seeds u64 or
+        0 / None (1 each); the outputs as kmer_classes_device.  Complete on return.  Returns the stats or None."""
+        stats = (C.c_uint64 * len(CLASS_STATS))() if want_stats else None
+        rc = self._L.gcsa2_seed_classes_device(self._h, d_group_offsets or None, int(n_groups), d_seeds or None, int(n_seeds), d_weights or None,
+                                               int(hit_max), int(shift), int(flags), d_class_of_bin or None, int(n_bins), int(n_classes),
+                                               d_votes or None, d_calls or None, stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None
 
     def lf_node_batch(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)

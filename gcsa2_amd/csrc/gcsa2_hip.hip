@@ -21,6 +21,7 @@
 //   kernels_seeds.hpp   k_capped_seeds        GCSA::LF(range, comp) + GCSA::count per step: the shortest matches under an occurrence cap
 //                                                                        include/gcsa/gcsa.h:155-162, src/gcsa.cpp:802-809
 //   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
+//   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
 //   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
@@ -59,6 +60,7 @@ using namespace g2;
 #include "kernels_submem.hpp"
 #include "kernels_seeds.hpp"
 #include "kernels_support.hpp"
+#include "kernels_classes.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -6052,6 +6054,370 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   if(stats != nullptr) { *stats = sums; }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_support_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== k-mer classes: per read, the votes of its k-mers (or any seed records) over classes of graph nodes (kernels_classes.hpp) ====
+namespace {
+
+// what every form refuses before any device is touched, then the components the call needs (no LCP array)
+int classes_checks(const gcsa2_index* ix, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name)
+{
+  CHECK_INDEX(ix);
+  if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: shift must be below 64"); }
+  if((flags & ~(GCSA2_CLASS_PER_WINDOW | GCSA2_CLASS_UNAMBIGUOUS)) != 0)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: unknown flags (GCSA2_CLASS_PER_WINDOW, GCSA2_CLASS_UNAMBIGUOUS)");
+  }
+  if(n_classes == 0 || n_classes > GCSA2_CLASS_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: n_classes must be 1 .. GCSA2_CLASS_LIMIT (4096)"); }
+  if(class_of_bin == nullptr && n_bins > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string("classes: ") + map_name + " is NULL with n_bins > 0"); }
+  return locate_checks(ix, 0);
+}
+
+int kmer_classes_checks(const gcsa2_index* ix, u64 k, u64 stride, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name)
+{
+  CHECK_INDEX(ix);
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: k must be at least 1"); }
+  if(stride == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: stride must be at least 1"); }
+  return classes_checks(ix, shift, flags, class_of_bin, n_bins, n_classes, map_name);
+}
+
+// what a call votes with and writes
+struct ClassesJob
+{
+  u64 hit_max, shift; int flags;
+  const u32* class_of_bin; u64 n_bins, n_classes;
+  u64* votes; gcsa2_class_call* calls;
+};
+
+// Steps 2 onward of a classes call.  m (< 2^32) records of `words` u64 with (sp, ep) at words 2 and 3, their count()s in
+// `known` or (nullptr) computed here, weights or (nullptr) 1 each.  n_groups (1 <= n_groups < 2^32) groups: with `windows`,
+// group q owns the windows [group_off[q], group_off[q + 1]) of a search of `limit` windows whose wavefronts left wave_base /
+// wave_mask; otherwise the records [group_off[q], group_off[q + 1]), limit = m.  Writes every row and call and fills every
+// field of *st_out but `windows`.  Host round trips: those of support_tail.  Scratch: per record 28 bytes; per counted record
+// 36 bytes and the sorts' temporaries; per distinct range 56 bytes; per value that the distinct ranges count() 8 bytes (the
+// signatures, which stay); per chunk -- the same buffers for every chunk -- 8 bytes per range and 28 1/8 bytes per value of
+// the largest, and hipCUB's.  A range of 2^31 or more values is refused (one run-length encoding per chunk).
+int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* known, const u64* weights, u64 m, bool windows, const u64* group_off,
+                 u64 n_groups, u64 limit, const u32* wave_base, const u64* wave_mask, const ClassesJob& job, gcsa2_class_stats* st_out,
+                 Scratch& scratch, hipStream_t st)
+{
+  unsigned long long* stat = nullptr;
+  u32 *slot = nullptr, *run_of = nullptr;
+  u64 *span = nullptr, *sig = nullptr;
+  HIP_TRY(scratch.get(stat, CLS_WORDS));
+  HIP_TRY(hipMemsetAsync(stat, 0, CLS_WORDS * sizeof(unsigned long long), st));
+  scratch.settled = false;
+  unsigned long long host_stat[CLS_WORDS];
+  // the last step, from wherever the records run out: every row and call is written, with or without a counted record
+  auto vote = [&]() -> int
+  {
+    const u64 resident = u64(ix->compute_units) * 32;              // one wavefront per workgroup
+    const dim3 grid(unsigned(std::min<u64>(n_groups, resident)));
+    const size_t lds = size_t(job.n_classes) * sizeof(u64);
+    if(windows) { hipLaunchKernelGGL((k_classes_vote<true>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
+    else { hipLaunchKernelGGL((k_classes_vote<false>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
+    LAUNCH_CHECK("k_classes_vote");
+    HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    scratch.settled = true;
+    st_out->votes = host_stat[CLS_VOTES];
+    st_out->unclassified = host_stat[CLS_UNCLASSIFIED];
+    st_out->ambiguous = host_stat[CLS_AMBIGUOUS];
+    return GCSA2_OK;
+  };
+  if(m == 0) { return vote(); }
+  // 1. the cap first: only the counted records reach the sort; every record keeps its compacted place
+  u64 *csp = nullptr, *cep = nullptr, *ccnt = nullptr;
+  HIP_TRY(scratch.get(slot, m));
+  HIP_TRY(scratch.get(csp, m)); HIP_TRY(scratch.get(cep, m)); HIP_TRY(scratch.get(ccnt, m));
+  hipLaunchKernelGGL(k_classes_fold, dim3(unsigned((m + CLASSES_FOLD_TPB - 1) / CLASSES_FOLD_TPB)), dim3(CLASSES_FOLD_TPB), 0, st, ix->img, recs, words, known, m, job.hit_max, stat, csp, cep, ccnt, slot);
+  LAUNCH_CHECK("k_classes_fold");
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const u64 c = host_stat[CLS_CURSOR] & 0xFFFFFFFFull;
+  st_out->found = host_stat[CLS_CURSOR] >> 32;
+  st_out->counted = c;
+  if(c == 0) { return vote(); }
+  // 2. equal ranges fold, as support_tail does; the runs' multiplicities are not needed, their numbers per record are
+  u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
+  int bits = 1;
+  while(bits < 64 && (top >> bits) != 0) { bits++; }
+  u64 *key_a = nullptr, *key_b = nullptr, *ranges = nullptr, *run_counts = nullptr, *run_off = nullptr;
+  u32 *perm_a = nullptr, *perm_b = nullptr, *head = nullptr, *run = nullptr;
+  unsigned long long* mult = nullptr;
+  char* tmp = nullptr;
+  HIP_TRY(scratch.get(key_a, c)); HIP_TRY(scratch.get(key_b, c));
+  HIP_TRY(scratch.get(perm_a, c)); HIP_TRY(scratch.get(perm_b, c));
+  HIP_TRY(scratch.get(head, c)); HIP_TRY(scratch.get(run, c)); HIP_TRY(scratch.get(run_of, c));
+  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, head, run, size_t(c), st));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, key_a, key_b, size_t(c + 1), st));
+  HIP_TRY(scratch.get(tmp, std::max(sort_bytes, std::max(scan_bytes, sum_bytes))));
+  hipLaunchKernelGGL(k_support_iota, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, c);
+  LAUNCH_CHECK("k_support_iota");
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));      // perm_b: by ep
+  hipLaunchKernelGGL(k_support_gather, dim3(grid_for(c)), dim3(TPB), 0, st, csp, perm_b, c, key_a);
+  LAUNCH_CHECK("k_support_gather");
+  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, perm_b, perm_a, size_t(c), 0, bits, st));    // key_b, perm_a: by (sp, ep)
+  hipLaunchKernelGGL(k_support_heads, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, perm_a, c, head);
+  LAUNCH_CHECK("k_support_heads");
+  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, scan_bytes, head, run, size_t(c), st));
+  hipLaunchKernelGGL(k_classes_run_of, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, run, c, run_of);
+  LAUNCH_CHECK("k_classes_run_of");
+  u32 d32 = 0;
+  HIP_TRY(hipMemcpyAsync(&d32, run + (c - 1), sizeof(u32), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const u64 d = d32;
+  st_out->distinct = d;
+  HIP_TRY(scratch.get(ranges, 2 * d)); HIP_TRY(scratch.get(run_counts, d + 1)); HIP_TRY(scratch.get(run_off, d + 1)); HIP_TRY(scratch.get(mult, d));
+  HIP_TRY(scratch.get(span, 2 * d));
+  HIP_TRY(hipMemsetAsync(mult, 0, d * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(span, 0, 2 * d * sizeof(u64), st));
+  HIP_TRY(hipMemsetAsync(run_counts + d, 0, sizeof(u64), st));
+  hipLaunchKernelGGL(k_support_runs, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, ccnt, static_cast<const u64*>(nullptr), perm_a, run, c, ranges, run_counts, mult);
+  LAUNCH_CHECK("k_support_runs");
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, sum_bytes, run_counts, run_off, size_t(d + 1), st));
+  // 3. the chunks, as support_tail cuts them
+  const u64 budget = support_chunk_budget();
+  struct Chunk { u64 q0, q1, raw; };
+  std::vector<Chunk> chunks;
+  unsigned long long* d_cut = stat + CLS_CUT;
+  u64 most_runs = 0, most_raw = 0, all_raw = 0;
+  for(u64 q0 = 0; q0 < d; )
+  {
+    unsigned long long cut[2] = {0, 0};
+    hipLaunchKernelGGL(k_support_cut, dim3(1), dim3(1), 0, st, run_off, d, q0, budget, ix->tune.locate_split_queries, d_cut);
+    LAUNCH_CHECK("k_support_cut");
+    HIP_TRY(hipMemcpyAsync(cut, d_cut, sizeof(cut), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const u64 q1 = cut[0], raw = cut[1];
+    if(q1 <= q0 || q1 > d) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "classes: a chunk without a range"); }
+    chunks.push_back(Chunk{q0, q1, raw});
+    most_runs = std::max(most_runs, q1 - q0); most_raw = std::max(most_raw, raw); all_raw += raw;
+    q0 = q1;
+  }
+  // 4. locate and sign, chunk by chunk, in the same scratch; the signatures of all chunks stay, one entry per value at most
+  u64 *off = nullptr, *val = nullptr, *owners = nullptr, *keys = nullptr, *sorted = nullptr;
+  u32 *lengths = nullptr, *n_entries = nullptr;
+  char* cub = nullptr;
+  if(most_raw >= (u64(1) << 31)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "classes: a range with 2^31 or more values; set hit_max"); }
+  HIP_TRY(scratch.get(off, most_runs + 1)); HIP_TRY(scratch.get(val, most_raw)); HIP_TRY(scratch.get(owners, most_raw / OWNER_SPAN + 3));
+  HIP_TRY(scratch.get(keys, most_raw)); HIP_TRY(scratch.get(sorted, most_raw)); HIP_TRY(scratch.get(lengths, most_raw)); HIP_TRY(scratch.get(n_entries, 1));
+  HIP_TRY(scratch.get(sig, all_raw));
+  int run_bits = 1;
+  while(run_bits < 50 && (most_runs >> run_bits) != 0) { run_bits++; }
+  const int key_bits = int(CLASS_KEY_BITS) + run_bits;
+  size_t keys_bytes = 0, rle_bytes = 0;
+  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, keys_bytes, keys, sorted, size_t(most_raw > 0 ? most_raw : 1), 0, key_bits, st));
+  HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, sorted, keys, lengths, n_entries, int(most_raw > 0 ? most_raw : 1), st));
+  HIP_TRY(scratch.get(cub, std::max(keys_bytes, rle_bytes)));
+  u64 values = 0;
+  for(const Chunk& chunk : chunks)
+  {
+    const u64 runs = chunk.q1 - chunk.q0;
+    u64 total = 0;
+    ValuesProvider provide = [val, most_raw](u64 count) -> u64* { return count <= most_raw ? val : nullptr; };
+    const int rc = locate_core(ix, ranges + 2 * chunk.q0, runs, 1, off, provide, &total, st, val, most_raw);
+    if(rc != GCSA2_OK) { return rc; }
+    if(total == 0) { continue; }
+    if(total > most_raw || values + total > all_raw) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "classes: a chunk with more values than its ranges count"); }
+    const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, off, runs, total, OWNER_SPAN, spans, owners);
+    LAUNCH_CHECK("k_block_owners");
+    hipLaunchKernelGGL(k_classes_keys, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, u32(job.n_classes), keys);
+    LAUNCH_CHECK("k_classes_keys");
+    scratch.settled = false;
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(cub, keys_bytes, keys, sorted, size_t(total), 0, key_bits, st));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(cub, rle_bytes, sorted, keys, lengths, n_entries, int(total), st));
+    hipLaunchKernelGGL(k_classes_sign, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span);
+    LAUNCH_CHECK("k_classes_sign");
+    values += total;
+  }
+  st_out->values = values;
+  // 5. the votes
+  return vote();
+}
+
+// gcsa2_kmer_classes_device after its argument checks (0 < n_patterns < 2^32): the search of gcsa2_kmer_support_device, with
+// room for every window, so that it runs once; its records stay in arrival order, and what its wavefronts leave (SeedEmit's
+// base and mask) is how a read finds them.
+int kmer_classes_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
+                      const ClassesJob& job, gcsa2_class_stats* st_out, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *sizes = nullptr, *woff = nullptr;
+  char* scan_tmp = nullptr;
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  HIP_TRY(scratch.get(woff, n_patterns + 1));
+  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
+  LAUNCH_CHECK("k_window_counts");
+  size_t scan_bytes = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
+  u64 total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more windows in one call; split the batch"); }
+  st_out->windows = total;
+  if(total == 0) { return classes_tail(ix, nullptr, 4, nullptr, nullptr, 0, true, woff, n_patterns, 0, nullptr, nullptr, job, st_out, scratch, st); }
+  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
+  u64* owners = nullptr;
+  SeedEmit emit{};
+  HIP_TRY(scratch.get(owners, spans + 1));
+  HIP_TRY(scratch.get(emit.cursor, 1));
+  HIP_TRY(scratch.get(emit.base, spans));
+  HIP_TRY(scratch.get(emit.found, spans + 1));
+  HIP_TRY(scratch.get(emit.mask, spans));
+  emit.capacity = total;
+  HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
+  HIP_TRY(scratch.get(emit.counts, emit.capacity));
+  scratch.settled = false;
+  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
+  LAUNCH_CHECK("k_block_owners");
+  HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
+  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
+  gcsa2_kmer_profile* const no_profiles = nullptr;
+  if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
+  else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
+  LAUNCH_CHECK("k_kmer_seeds");
+  u64 m = 0;
+  HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if(m > emit.capacity) { return fail(GCSA2_ERR_HIP, "kmer_classes: more seeds than windows"); }
+  return classes_tail(ix, emit.recs, 4, emit.counts, nullptr, m, true, woff, n_patterns, total, emit.base, emit.mask, job, st_out, scratch, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_classes_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                              uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
+                              uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream)
+{
+  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls};
+  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_device: ") + e.what()); }
+}
+
+int gcsa2_seed_classes_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                              const uint64_t* d_weights, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin,
+                              uint64_t n_bins, uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats,
+                              void* stream)
+{
+  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_seeds is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more seeds in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.windows = n_seeds;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls};
+  {
+    Scratch scratch(ix, st);
+    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
+                      job, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_classes_device: ") + e.what()); }
+}
+
+// The host form.  The class map goes to the device once; the reads travel in pieces of whole reads (tune.ms_piece_bytes,
+// cut_pieces) on tune.ms_threads host threads, each piece one gcsa2_kmer_classes_device on its thread's stream into device
+// rows and calls of its own, which are copied to the piece's place in the caller's arrays: a row belongs to one read.
+int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                             uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* class_of_bin, uint64_t n_bins,
+                             uint64_t n_classes, uint64_t* votes, gcsa2_class_call* calls, gcsa2_class_stats* stats)
+{
+  int rc = kmer_classes_checks(ix, k, stride, shift, flags, class_of_bin, n_bins, n_classes, "class_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: offsets is NULL"); }
+  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: patterns is NULL"); }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  u64 windows_all = 0;
+  for(u64 q = 0; q < n_patterns; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    if(len >= k) { windows_all += (len - k) / stride + 1; }
+  }
+  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more windows in one call; split the batch"); }
+  DeviceGuard guard(ix->device);
+  DBuf<u32> d_map;
+  HIP_TRY(d_map.alloc(n_bins));
+  if(n_bins > 0) { HIP_TRY(hipMemcpy(d_map.p, class_of_bin, n_bins * sizeof(u32), hipMemcpyHostToDevice)); }
+  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
+                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
+  const u64 pieces = cut.size() - 1;
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  std::vector<gcsa2_class_stats> done(pieces);
+  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard piece_guard(ix->device);
+    std::vector<u64> local;
+    hipStream_t stream = nullptr;
+    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      DBuf<u8> d_pat; DBuf<u64> d_off, d_votes; DBuf<gcsa2_class_call> d_calls;
+      hipError_t e = d_pat.alloc(bytes + 16);
+      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
+      if(e == hipSuccess && votes != nullptr) { e = d_votes.alloc(count * n_classes); }
+      if(e == hipSuccess && calls != nullptr) { e = d_calls.alloc(count); }
+      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
+      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
+      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
+      const int piece_rc = gcsa2_kmer_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes,
+                                                     votes != nullptr ? d_votes.p : nullptr, calls != nullptr ? d_calls.p : nullptr, &done[c], stream);
+      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
+      if(votes != nullptr) { e = hipMemcpy(votes + b * n_classes, d_votes.p, count * n_classes * sizeof(u64), hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && calls != nullptr) { e = hipMemcpy(calls + b, d_calls.p, count * sizeof(gcsa2_class_call), hipMemcpyDeviceToHost); }
+      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
+    }
+    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  for(const gcsa2_class_stats& s : done)
+  {
+    sums.windows += s.windows; sums.found += s.found; sums.counted += s.counted; sums.distinct += s.distinct; sums.values += s.values;
+    sums.votes += s.votes; sums.unclassified += s.unclassified; sums.ambiguous += s.ambiguous;
+  }
+  if(stats != nullptr) { *stats = sums; }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -373,6 +373,27 @@ public:
     check(rc, "GCSA::kmer_support_batch()");
   }
 
+  // A read classifier's or binner's lookup in one call (gcsa2_kmer_classes_batch): every window P_q[j stride, j stride + k) with
+  // a non-empty find() and hit_max == 0 or count(range) <= hit_max votes, in the row of its read, for the class
+  // class_of_bin[v >> shift] of every located value v of its range (GCSA2_CLASS_NONE, an id >= n_classes or a bin beyond the
+  // map: no class).  flags: GCSA2_CLASS_PER_WINDOW, GCSA2_CLASS_UNAMBIGUOUS.  votes (reads x n_classes, row-major) and calls
+  // (one per read) are resized and WRITTEN.  Needs no LCP array.
+  void kmer_classes_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type stride,
+                          size_type hit_max, size_type shift, int flags, const std::vector<std::uint32_t>& class_of_bin, size_type n_classes,
+                          std::vector<size_type>& votes, std::vector<gcsa2_class_call>& calls, gcsa2_class_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    votes.assign(np * n_classes, 0);
+    calls.assign(np, gcsa2_class_call{GCSA2_UNKNOWN, 0, GCSA2_UNKNOWN, 0, 0, 0});
+    const int rc = gcsa2_kmer_classes_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                            k, stride, hit_max, shift, flags, class_of_bin.empty() ? nullptr : class_of_bin.data(),
+                                            class_of_bin.size(), n_classes, votes.empty() ? nullptr : votes.data(),
+                                            calls.empty() ? nullptr : calls.data(), stats);
+    check(rc, "GCSA::kmer_classes_batch()");
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).

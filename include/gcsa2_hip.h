@@ -858,6 +858,87 @@ int gcsa2_kmer_support_batch(const gcsa2_index* index, const uint8_t* patterns, 
 int gcsa2_seed_support_device(const gcsa2_index* index, const gcsa2_mem* d_seeds, uint64_t n_seeds,
                               const uint64_t* d_weights /* or NULL = 1 each */, uint64_t hit_max, uint64_t shift, int flags,
                               uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream);
+/* ---- k-mer classes: per read, the votes of its k-mers (or any seed records) over classes of graph nodes -----------------------
+ * The transpose of k-mer support, for a read classifier or binner: per READ, on which class of graph nodes -- chromosome,
+ * contig, subgraph, host or contaminant -- do its k-mers land?  With gcsa2_kmer_hits_batch the caller would pull every hit of
+ * every window across the link, map hit >> shift through its node -> class table, remove duplicate classes per window and
+ * scatter-add into a reads x classes matrix; here the search, the fold of equal ranges and the locate of every distinct range
+ * (ONCE, however many reads carry its k-mer) are those of k-mer support, and what leaves the device is one row of n_classes
+ * counters per read, or only the call.  (d_patterns, d_offsets, n_patterns), k and stride are those of gcsa2_kmer_windows_device.
+ *
+ * DEFINITION.
+ *   - The windows, FOUND and COUNTED are exactly those of gcsa2_kmer_support_device for (k, stride, hit_max): a found window is
+ *     counted if hit_max == 0 or count(range) <= hit_max; a range with count() == 0 is not counted; there is no sampling.
+ *   - class(v) of a located value v: b = v >> shift (unsigned); if b < n_bins and d_class_of_bin[b] < n_classes it is
+ *     d_class_of_bin[b], otherwise v has NO CLASS: GCSA2_CLASS_NONE, any id >= n_classes and a bin beyond the map mean the same.
+ *   - Per range R with V(R) = the sorted distinct values of gcsa2_locate_into(R, sort = 1): n_c(R) = the values of V(R) with
+ *     class c, none(R) = those without a class, classes(R) = the number of classes with n_c(R) > 0.
+ *   - A counted record of weight w (1 for k-mer windows) and range R adds x_c to votes[q][c] of its read or group q: by default
+ *     x_c = w n_c(R); with GCSA2_CLASS_PER_WINDOW x_c = w for every c with n_c(R) > 0; with GCSA2_CLASS_UNAMBIGUOUS x_c = 0 for
+ *     all c unless classes(R) == 1.  Sums are taken in 64-bit arithmetic.
+ *   - Rows are WRITTEN, not added to: the call writes every entry of d_votes[0 .. n_patterns n_classes) (row-major) and of
+ *     d_calls[0 .. n_patterns), and nothing behind them.
+ *   - call(q): total = the row's sum; best = the class with the most votes, the lowest id on a tie, or GCSA2_UNKNOWN (with
+ *     best_votes = 0) when no class has a vote; second = the class with the most votes among the others that has at least one
+ *     vote, the lowest id on a tie, or GCSA2_UNKNOWN with second_votes = 0 when there is none; counted = the number of counted
+ *     records of q, unweighted.
+ *   - stats (host, may be NULL): windows, found, counted, distinct and values as in gcsa2_support_stats; votes = the sum of all
+ *     row totals; unclassified = the sum of none(R) over the counted records, unweighted; ambiguous = the number of counted
+ *     records with classes(R) >= 2 -- with and without GCSA2_CLASS_UNAMBIGUOUS; with it these are the records that did not vote.
+ *   - d_votes, d_calls and stats may each be NULL; all three NULL is valid and does the work.  Without d_votes the matrix does
+ *     not exist in device memory either: a row lives in on-chip memory while its read is summed.
+ *
+ * GCSA2_ERR_INVALID_ARGUMENT, with nothing written (stats included) and before any device is touched: a NULL index, k == 0,
+ * stride == 0, shift >= 64, an unknown flag, n_classes == 0 or n_classes > GCSA2_CLASS_LIMIT, d_class_of_bin == NULL with
+ * n_bins > 0.  n_bins == 0 is valid: everything is unclassified.  Needs the samples and the counters
+ * (GCSA2_ERR_MISSING_COMPONENT, likewise), not the LCP array.  2^32 or more reads, windows, groups or seeds:
+ * GCSA2_ERR_BUFFER_TOO_SMALL ("split the batch"); likewise a single counted range with 2^31 or more values (set hit_max).
+ * n_patterns == 0 or n_groups == 0 is GCSA2_OK with zero stats.  On an error
+ * after work has begun rows and calls are unspecified and stats is not written.  Enqueued on `stream`, complete on return.
+ *
+ * The records of the search stay where they arrived; a read finds the record of a window through the 16 bytes that every
+ * wavefront of the search leaves.  The cap, the sorts, the runs and the chunks (GCSA2_SUPPORT_CHUNK) are those of k-mer
+ * support.  Every chunk's values become keys (run, class) that are sorted and run-length encoded into the runs' signatures --
+ * equal classes are NOT neighbours in value order -- which are kept for all runs: scratch of 8 bytes per located value of the
+ * distinct ranges, not per hit.  Then one wavefront per read adds its records' signatures into n_classes 64-bit counters in
+ * LDS (at most 32 KB), stores the row with plain stores and reduces best and second: no global atomic but three per workgroup
+ * for the stats. */
+#define GCSA2_CLASS_NONE        0xFFFFFFFFu   /* a bin without a class */
+#define GCSA2_CLASS_LIMIT       4096          /* n_classes may be 1 .. GCSA2_CLASS_LIMIT */
+#define GCSA2_CLASS_PER_WINDOW  1   /* a record votes once per class, however many of its values fall into it */
+#define GCSA2_CLASS_UNAMBIGUOUS 2   /* only records whose values fall into exactly one class vote */
+typedef struct gcsa2_class_call  { uint64_t best, best_votes, second, second_votes, total, counted; } gcsa2_class_call;
+typedef struct gcsa2_class_stats { uint64_t windows, found, counted, distinct, values, votes, unclassified, ambiguous; } gcsa2_class_stats;
+int gcsa2_kmer_classes_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                              uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                              const uint32_t* d_class_of_bin, uint64_t n_bins, uint64_t n_classes,
+                              uint64_t* d_votes /* n_patterns x n_classes, row-major, or NULL */,
+                              gcsa2_class_call* d_calls /* n_patterns, or NULL */,
+                              gcsa2_class_stats* stats /* host, may be NULL */, void* stream);
+/* The same for reads and the class map in host memory, into host arrays: offsets[0] == 0, decreasing offsets are refused
+ * (GCSA2_ERR_INVALID_ARGUMENT).  A batch of two pieces' worth of read bytes or more travels in pieces of whole reads
+ * (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS, as the MEM calls); the class map is uploaded once per call.  Rows and calls are exact
+ * whatever the pieces (a row belongs to one read); stats are summed over the pieces: distinct and values are then per-piece
+ * sums, an upper bound of the whole-batch figures.  On an error votes and calls may be partly written.  Complete on return. */
+int gcsa2_kmer_classes_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                             uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                             const uint32_t* class_of_bin, uint64_t n_bins, uint64_t n_classes,
+                             uint64_t* votes /* host, n_patterns x n_classes, or NULL */, gcsa2_class_call* calls /* host, or NULL */,
+                             gcsa2_class_stats* stats);
+/* The same votes over seed records the caller already has on the device, in groups: group g owns the records
+ * [d_group_offsets[g], d_group_offsets[g + 1]) -- the seed CSRs that the MEM hits, k-mer hits and capped seeds emit, as they
+ * are -- with a weight per record (d_weights, n_seeds entries, or NULL = 1 each; 0 is allowed).  Only sp and ep of a record are
+ * read: count() is evaluated again.  A record with an empty range (either form) contributes nothing.  A group whose offsets
+ * decrease or reach beyond n_seeds is NOT READ: its row is zero and its call {GCSA2_UNKNOWN, 0, GCSA2_UNKNOWN, 0, 0, 0} -- the
+ * rule of gcsa2_extend_device for an invalid state, so that no read-back is needed to refuse it and a bad cursor cannot fault.
+ * stats.windows = n_seeds; found, counted, distinct and values are taken over all n_seeds records, as gcsa2_seed_support_device
+ * does; votes, unclassified and ambiguous over the records as their groups own them (the same thing when the groups are a
+ * CSR over the records).  n_groups == 0 is GCSA2_OK with zero stats; d_group_offsets == NULL with n_groups > 0 and d_seeds ==
+ * NULL with n_seeds > 0 are GCSA2_ERR_INVALID_ARGUMENT.  Refusals, limits and everything else as above. */
+int gcsa2_seed_classes_device(const gcsa2_index* index, const uint64_t* d_group_offsets, uint64_t n_groups,
+                              const gcsa2_mem* d_seeds, uint64_t n_seeds, const uint64_t* d_weights /* or NULL = 1 each */,
+                              uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
+                              uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
