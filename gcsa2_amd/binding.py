@@ -27,6 +27,10 @@ CLASS_PER_WINDOW = 1        # GCSA2_CLASS_PER_WINDOW
 CLASS_UNAMBIGUOUS = 2       # GCSA2_CLASS_UNAMBIGUOUS
 CLASS_CALL = ("best", "best_votes", "second", "second_votes", "total", "counted")     # gcsa2_class_call
 CLASS_STATS = ("windows", "found", "counted", "distinct", "values", "votes", "unclassified", "ambiguous")     # gcsa2_class_stats
+TOP_LIMIT = 64              # GCSA2_TOP_LIMIT
+TOP_SLOTS_DEFAULT = 512     # the default of GCSA2_TOP_SLOTS (the test knob of the top-classes calls)
+CLASS_VOTE = np.dtype([("class_id", np.uint64), ("votes", np.uint64)])     # gcsa2_class_vote
+TOP_SUMMARY = np.dtype([("voted", np.uint64), ("total", np.uint64), ("counted", np.uint64)])     # gcsa2_top_summary
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -55,6 +59,7 @@ EXPORTS = [
     "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
     "gcsa2_kmer_support_device", "gcsa2_kmer_support_batch", "gcsa2_seed_support_device",
     "gcsa2_kmer_classes_device", "gcsa2_kmer_classes_batch", "gcsa2_seed_classes_device",
+    "gcsa2_kmer_top_classes_device", "gcsa2_kmer_top_classes_batch", "gcsa2_seed_top_classes_device",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -184,6 +189,9 @@ def load_library():
     L.gcsa2_kmer_classes_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
     L.gcsa2_kmer_classes_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp]
     L.gcsa2_seed_classes_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_kmer_top_classes_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_kmer_top_classes_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp]
+    L.gcsa2_seed_top_classes_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp, vp]
     L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -746,6 +754,50 @@ class GCSA:
         rc = self._L.gcsa2_seed_classes_device(self._h, d_group_offsets or None, int(n_groups), d_seeds or None, int(n_seeds), d_weights or None,
                                                int(hit_max), int(shift), int(flags), d_class_of_bin or None, int(n_bins), int(n_classes),
                                                d_votes or None, d_calls or None, stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None
+
+    def kmer_top_classes_batch(self, patterns, offsets, k, class_of_bin, n_classes, top_n, stride=1, hit_max=0, shift=11, per_window=False,
+                               unambiguous=False, top=True, summaries=True):
+        """Per read, the top_n classes with the most votes of its k-mers (gcsa2_kmer_top_classes_batch): (top, summaries, stats).
+        The votes are those of kmer_classes_batch, but n_classes may be up to 0xFFFFFFFF and no matrix exists.  top: (reads, top_n)
+        of CLASS_VOTE, more votes first and the lower id on a tie, {UNKNOWN, 0} behind the voted classes; summaries: (reads,) of
+        TOP_SUMMARY; either is None when not asked for.  stats: a dict of CLASS_STATS."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        class_of_bin = np.ascontiguousarray(class_of_bin, dtype=np.uint32)
+        n = max(offsets.shape[0], 1) - 1
+        out_top = np.zeros((n, max(int(top_n), 0)), dtype=CLASS_VOTE) if top else None
+        out_sums = np.zeros(n, dtype=TOP_SUMMARY) if summaries else None
+        stats = (C.c_uint64 * len(CLASS_STATS))()
+        flags = (CLASS_PER_WINDOW if per_window else 0) | (CLASS_UNAMBIGUOUS if unambiguous else 0)
+        _check(self._L.gcsa2_kmer_top_classes_batch(self._h, _p8(patterns), _p64(offsets), n, int(k), int(stride), int(hit_max), int(shift), flags,
+                                                    class_of_bin.ctypes.data if class_of_bin.shape[0] else None, class_of_bin.shape[0], int(n_classes),
+                                                    int(top_n), out_top.ctypes.data if top else None, out_sums.ctypes.data if summaries else None, stats))
+        return out_top, out_sums, dict(zip(CLASS_STATS, (int(x) for x in stats)))
+
+    def kmer_top_classes_device(self, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_class_of_bin, n_bins, n_classes,
+                                top_n, d_top, d_summaries, stream=0, want_stats=True):
+        """gcsa2_kmer_top_classes_device on caller-owned device buffers (raw pointers): d_class_of_bin n_bins u32, d_top n_patterns x
+        top_n records of two u64 and d_summaries n_patterns records of three u64, both written (0 / None: not wanted).  Complete
+        on return.  Returns the stats as a dict of CLASS_STATS, or None with want_stats=False (a NULL stats pointer)."""
+        stats = (C.c_uint64 * len(CLASS_STATS))() if want_stats else None
+        rc = self._L.gcsa2_kmer_top_classes_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), int(shift), int(flags),
+                                                   d_class_of_bin or None, int(n_bins), int(n_classes), int(top_n), d_top or None, d_summaries or None,
+                                                   stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None
+
+    def seed_top_classes_device(self, d_group_offsets, n_groups, d_seeds, n_seeds, d_weights, hit_max, shift, flags, d_class_of_bin, n_bins,
+                                n_classes, top_n, d_top, d_summaries, stream=0, want_stats=True):
+        """gcsa2_seed_top_classes_device on caller-owned device buffers (raw pointers): groups, records and weights as
+        seed_classes_device, the outputs as kmer_top_classes_device.  Complete on return.  Returns the stats or None."""
+        stats = (C.c_uint64 * len(CLASS_STATS))() if want_stats else None
+        rc = self._L.gcsa2_seed_top_classes_device(self._h, d_group_offsets or None, int(n_groups), d_seeds or None, int(n_seeds), d_weights or None,
+                                                   int(hit_max), int(shift), int(flags), d_class_of_bin or None, int(n_bins), int(n_classes),
+                                                   int(top_n), d_top or None, d_summaries or None, stats, stream)
         if rc != 0:
             raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
         return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None

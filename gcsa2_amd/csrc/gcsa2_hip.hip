@@ -6062,7 +6062,8 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
 namespace {
 
 // what every form refuses before any device is touched, then the components the call needs (no LCP array)
-int classes_checks(const gcsa2_index* ix, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name)
+int classes_checks(const gcsa2_index* ix, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name, u64 top_n = 0,
+                   bool sparse = false)
 {
   CHECK_INDEX(ix);
   if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: shift must be below 64"); }
@@ -6070,26 +6071,51 @@ int classes_checks(const gcsa2_index* ix, u64 shift, int flags, const void* clas
   {
     return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: unknown flags (GCSA2_CLASS_PER_WINDOW, GCSA2_CLASS_UNAMBIGUOUS)");
   }
-  if(n_classes == 0 || n_classes > GCSA2_CLASS_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: n_classes must be 1 .. GCSA2_CLASS_LIMIT (4096)"); }
+  if(sparse)
+  {
+    if(n_classes == 0 || n_classes > 0xFFFFFFFFull) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "top_classes: n_classes must be 1 .. 0xFFFFFFFF"); }
+    if(top_n == 0 || top_n > GCSA2_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "top_classes: top_n must be 1 .. GCSA2_TOP_LIMIT (64)"); }
+  }
+  else if(n_classes == 0 || n_classes > GCSA2_CLASS_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "classes: n_classes must be 1 .. GCSA2_CLASS_LIMIT (4096)"); }
   if(class_of_bin == nullptr && n_bins > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string("classes: ") + map_name + " is NULL with n_bins > 0"); }
   return locate_checks(ix, 0);
 }
 
-int kmer_classes_checks(const gcsa2_index* ix, u64 k, u64 stride, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name)
+int kmer_classes_checks(const gcsa2_index* ix, u64 k, u64 stride, u64 shift, int flags, const void* class_of_bin, u64 n_bins, u64 n_classes, const char* map_name,
+                        u64 top_n = 0, bool sparse = false)
 {
   CHECK_INDEX(ix);
   if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: k must be at least 1"); }
   if(stride == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: stride must be at least 1"); }
-  return classes_checks(ix, shift, flags, class_of_bin, n_bins, n_classes, map_name);
+  return classes_checks(ix, shift, flags, class_of_bin, n_bins, n_classes, map_name, top_n, sparse);
 }
 
-// what a call votes with and writes
+// what a call votes with and writes: the dense form (votes, calls) or, with top_n != 0, the sparse one (top, summaries), whose
+// keys and signatures are the wide ones
 struct ClassesJob
 {
   u64 hit_max, shift; int flags;
   const u32* class_of_bin; u64 n_bins, n_classes;
   u64* votes; gcsa2_class_call* calls;
+  u64 top_n; gcsa2_class_vote* top; gcsa2_top_summary* summaries;
 };
+
+// GCSA2_TOP_SLOTS (a test knob, read per call): the slots of k_classes_top's table, a power of two (rounded down) between
+// TOP_SLOTS_MIN and TOP_SLOTS_MAX.  The result never depends on it.
+u32 top_slots()
+{
+  u64 slots = TOP_SLOTS_DEFAULT;
+  const char* env = std::getenv("GCSA2_TOP_SLOTS");
+  if(env != nullptr && *env != 0)
+  {
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(env, &end, 10);
+    if(end != env && *end == 0) { slots = std::min<u64>(std::max<u64>(v, TOP_SLOTS_MIN), TOP_SLOTS_MAX); }
+  }
+  u32 out = TOP_SLOTS_MIN;
+  while(u64(out) * 2 <= slots) { out *= 2; }
+  return out;
+}
 
 // Steps 2 onward of a classes call.  m (< 2^32) records of `words` u64 with (sp, ep) at words 2 and 3, their count()s in
 // `known` or (nullptr) computed here, weights or (nullptr) 1 each.  n_groups (1 <= n_groups < 2^32) groups: with `windows`,
@@ -6115,10 +6141,22 @@ int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* k
   {
     const u64 resident = u64(ix->compute_units) * 32;              // one wavefront per workgroup
     const dim3 grid(unsigned(std::min<u64>(n_groups, resident)));
-    const size_t lds = size_t(job.n_classes) * sizeof(u64);
-    if(windows) { hipLaunchKernelGGL((k_classes_vote<true>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
-    else { hipLaunchKernelGGL((k_classes_vote<false>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
-    LAUNCH_CHECK("k_classes_vote");
+    if(job.top_n != 0)
+    {
+      const u32 slots = top_slots();
+      const size_t lds = size_t(slots) * (sizeof(u64) + sizeof(u32));
+      const dim3 fit(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * std::min<u64>(32, (160u << 10) / lds))));   // as many as a CU's LDS holds
+      if(windows) { hipLaunchKernelGGL((k_classes_top<true>), fit, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, slots, u32(job.top_n), job.top, job.summaries, stat); }
+      else { hipLaunchKernelGGL((k_classes_top<false>), fit, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, slots, u32(job.top_n), job.top, job.summaries, stat); }
+      LAUNCH_CHECK("k_classes_top");
+    }
+    else
+    {
+      const size_t lds = size_t(job.n_classes) * sizeof(u64);
+      if(windows) { hipLaunchKernelGGL((k_classes_vote<true>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
+      else { hipLaunchKernelGGL((k_classes_vote<false>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
+      LAUNCH_CHECK("k_classes_vote");
+    }
     HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     scratch.settled = true;
@@ -6209,7 +6247,9 @@ int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* k
   HIP_TRY(scratch.get(sig, all_raw));
   int run_bits = 1;
   while(run_bits < 50 && (most_runs >> run_bits) != 0) { run_bits++; }
-  const int key_bits = int(CLASS_KEY_BITS) + run_bits;
+  const bool wide = job.top_n != 0;
+  if(wide && most_runs >= (u64(1) << 31)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "top_classes: a chunk with 2^31 or more ranges"); }
+  const int key_bits = int(wide ? WIDE_KEY_BITS : CLASS_KEY_BITS) + run_bits;
   size_t keys_bytes = 0, rle_bytes = 0;
   HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, keys_bytes, keys, sorted, size_t(most_raw > 0 ? most_raw : 1), 0, key_bits, st));
   HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, sorted, keys, lengths, n_entries, int(most_raw > 0 ? most_raw : 1), st));
@@ -6227,12 +6267,14 @@ int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* k
     const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
     hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, off, runs, total, OWNER_SPAN, spans, owners);
     LAUNCH_CHECK("k_block_owners");
-    hipLaunchKernelGGL(k_classes_keys, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, u32(job.n_classes), keys);
+    if(wide) { hipLaunchKernelGGL(k_classes_keys_wide, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, job.n_classes, keys); }
+    else { hipLaunchKernelGGL(k_classes_keys, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, u32(job.n_classes), keys); }
     LAUNCH_CHECK("k_classes_keys");
     scratch.settled = false;
     HIP_TRY(hipcub::DeviceRadixSort::SortKeys(cub, keys_bytes, keys, sorted, size_t(total), 0, key_bits, st));
     HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(cub, rle_bytes, sorted, keys, lengths, n_entries, int(total), st));
-    hipLaunchKernelGGL(k_classes_sign, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span);
+    if(wide) { hipLaunchKernelGGL(k_classes_sign_wide, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span); }
+    else { hipLaunchKernelGGL(k_classes_sign, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span); }
     LAUNCH_CHECK("k_classes_sign");
     values += total;
   }
@@ -6294,68 +6336,16 @@ int kmer_classes_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
   return classes_tail(ix, emit.recs, 4, emit.counts, nullptr, m, true, woff, n_patterns, total, emit.base, emit.mask, job, st_out, scratch, st);
 }
 
-}  // namespace
-
-extern "C" {
-
-int gcsa2_kmer_classes_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
-                              uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
-                              uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream)
-{
-  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: d_offsets is NULL"); }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls};
-  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_device: ") + e.what()); }
-}
-
-int gcsa2_seed_classes_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
-                              const uint64_t* d_weights, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin,
-                              uint64_t n_bins, uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats,
-                              void* stream)
-{
-  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_group_offsets is NULL"); }
-  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_seeds is NULL"); }
-  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more groups in one call; split the batch"); }
-  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more seeds in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.windows = n_seeds;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
-  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls};
-  {
-    Scratch scratch(ix, st);
-    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
-                      job, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_classes_device: ") + e.what()); }
-}
-
 // The host form.  The class map goes to the device once; the reads travel in pieces of whole reads (tune.ms_piece_bytes,
 // cut_pieces) on tune.ms_threads host threads, each piece one gcsa2_kmer_classes_device on its thread's stream into device
 // rows and calls of its own, which are copied to the piece's place in the caller's arrays: a row belongs to one read.
-int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
-                             uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* class_of_bin, uint64_t n_bins,
-                             uint64_t n_classes, uint64_t* votes, gcsa2_class_call* calls, gcsa2_class_stats* stats)
+// Both host forms: the dense one (top_n == 0: rows = votes, n_classes u64 per read; records = calls) and the sparse one (rows =
+// top, top_n gcsa2_class_vote per read; records = summaries).
+int classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max, u64 shift,
+                  int flags, const uint32_t* class_of_bin, u64 n_bins, u64 n_classes, bool sparse, u64 top_n, void* rows, void* records,
+                  gcsa2_class_stats* stats, const char* name)
 {
-  int rc = kmer_classes_checks(ix, k, stride, shift, flags, class_of_bin, n_bins, n_classes, "class_of_bin");
+  int rc = kmer_classes_checks(ix, k, stride, shift, flags, class_of_bin, n_bins, n_classes, "class_of_bin", top_n, sparse);
   if(rc != GCSA2_OK) { return rc; }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
   gcsa2_class_stats sums{};
@@ -6363,6 +6353,8 @@ int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: offsets is NULL"); }
   if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
   if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: patterns is NULL"); }
+  const u64 row_bytes = (sparse ? top_n * sizeof(gcsa2_class_vote) : n_classes * sizeof(u64));
+  const u64 record_bytes = (sparse ? sizeof(gcsa2_top_summary) : sizeof(gcsa2_class_call));
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
   u64 windows_all = 0;
@@ -6391,20 +6383,25 @@ int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, con
     {
       const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
       rebase_piece(offsets, b, count, local);
-      DBuf<u8> d_pat; DBuf<u64> d_off, d_votes; DBuf<gcsa2_class_call> d_calls;
+      DBuf<u8> d_pat, d_rows, d_records; DBuf<u64> d_off;
       hipError_t e = d_pat.alloc(bytes + 16);
       if(e == hipSuccess) { e = d_off.alloc(count + 1); }
-      if(e == hipSuccess && votes != nullptr) { e = d_votes.alloc(count * n_classes); }
-      if(e == hipSuccess && calls != nullptr) { e = d_calls.alloc(count); }
+      if(e == hipSuccess && rows != nullptr) { e = d_rows.alloc(count * row_bytes); }
+      if(e == hipSuccess && records != nullptr) { e = d_records.alloc(count * record_bytes); }
       if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
       if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
       if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
       if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      const int piece_rc = gcsa2_kmer_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes,
-                                                     votes != nullptr ? d_votes.p : nullptr, calls != nullptr ? d_calls.p : nullptr, &done[c], stream);
+      void* const piece_rows = (rows != nullptr ? d_rows.p : nullptr);
+      void* const piece_records = (records != nullptr ? d_records.p : nullptr);
+      const int piece_rc = (sparse ? gcsa2_kmer_top_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes, top_n,
+                                                                   static_cast<gcsa2_class_vote*>(piece_rows), static_cast<gcsa2_top_summary*>(piece_records),
+                                                                   &done[c], stream)
+                                   : gcsa2_kmer_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes,
+                                                               static_cast<u64*>(piece_rows), static_cast<gcsa2_class_call*>(piece_records), &done[c], stream));
       if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-      if(votes != nullptr) { e = hipMemcpy(votes + b * n_classes, d_votes.p, count * n_classes * sizeof(u64), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess && calls != nullptr) { e = hipMemcpy(calls + b, d_calls.p, count * sizeof(gcsa2_class_call), hipMemcpyDeviceToHost); }
+      if(rows != nullptr) { e = hipMemcpy(static_cast<u8*>(rows) + b * row_bytes, d_rows.p, count * row_bytes, hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && records != nullptr) { e = hipMemcpy(static_cast<u8*>(records) + b * record_bytes, d_records.p, count * record_bytes, hipMemcpyDeviceToHost); }
       if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
     }
     if(stream != nullptr) { (void)hipStreamDestroy(stream); }
@@ -6417,7 +6414,128 @@ int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   }
   if(stats != nullptr) { *stats = sums; }
   return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_batch: ") + e.what()); }
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_classes_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                              uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
+                              uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream)
+{
+  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls, 0, nullptr, nullptr};
+  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_device: ") + e.what()); }
+}
+
+int gcsa2_seed_classes_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                              const uint64_t* d_weights, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin,
+                              uint64_t n_bins, uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats,
+                              void* stream)
+{
+  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_seeds is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more seeds in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.windows = n_seeds;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls, 0, nullptr, nullptr};
+  {
+    Scratch scratch(ix, st);
+    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
+                      job, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_classes_device: ") + e.what()); }
+}
+
+int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                             uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* class_of_bin, uint64_t n_bins,
+                             uint64_t n_classes, uint64_t* votes, gcsa2_class_call* calls, gcsa2_class_stats* stats)
+{
+  return classes_batch(ix, patterns, offsets, n_patterns, k, stride, hit_max, shift, flags, class_of_bin, n_bins, n_classes, false, 0, votes, calls, stats,
+                       "gcsa2_kmer_classes_batch");
+}
+
+// ---- the sparse form: per read the top_n classes with the most votes, for any number of classes (k_classes_top) ----
+int gcsa2_kmer_top_classes_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                                  uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
+                                  uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
+                                  gcsa2_class_stats* stats, void* stream)
+{
+  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin", top_n, true);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_top_classes: d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_top_classes: 2^32 or more reads in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, nullptr, nullptr, top_n, d_top, d_summaries};
+  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_top_classes_device: ") + e.what()); }
+}
+
+int gcsa2_kmer_top_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                                 uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* class_of_bin, uint64_t n_bins,
+                                 uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* top, gcsa2_top_summary* summaries, gcsa2_class_stats* stats)
+{
+  return classes_batch(ix, patterns, offsets, n_patterns, k, stride, hit_max, shift, flags, class_of_bin, n_bins, n_classes, true, top_n, top, summaries, stats,
+                       "gcsa2_kmer_top_classes_batch");
+}
+
+int gcsa2_seed_top_classes_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                                  const uint64_t* d_weights, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin,
+                                  uint64_t n_bins, uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
+                                  gcsa2_class_stats* stats, void* stream)
+{
+  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin", top_n, true);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_top_classes: d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_top_classes: d_seeds is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_top_classes: 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_top_classes: 2^32 or more seeds in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.windows = n_seeds;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, nullptr, nullptr, top_n, d_top, d_summaries};
+  {
+    Scratch scratch(ix, st);
+    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
+                      job, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_top_classes_device: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -394,6 +394,27 @@ public:
     check(rc, "GCSA::kmer_classes_batch()");
   }
 
+  // The sparse form for any number of classes (gcsa2_kmer_top_classes_batch): the same votes, n_classes up to 0xFFFFFFFF, and
+  // per read the top_n (1 .. GCSA2_TOP_LIMIT) classes with the most votes -- more votes first, the lower id on a tie,
+  // {GCSA2_UNKNOWN, 0} behind the voted classes -- and {voted, total, counted}.  top (reads x top_n, row-major) and summaries
+  // (one per read) are resized and WRITTEN.  Needs no LCP array.
+  void kmer_top_classes_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type stride,
+                              size_type hit_max, size_type shift, int flags, const std::vector<std::uint32_t>& class_of_bin, size_type n_classes,
+                              size_type top_n, std::vector<gcsa2_class_vote>& top, std::vector<gcsa2_top_summary>& summaries,
+                              gcsa2_class_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    top.assign(np * (top_n <= GCSA2_TOP_LIMIT ? top_n : 0), gcsa2_class_vote{GCSA2_UNKNOWN, 0});
+    summaries.assign(np, gcsa2_top_summary{0, 0, 0});
+    const int rc = gcsa2_kmer_top_classes_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                                k, stride, hit_max, shift, flags, class_of_bin.empty() ? nullptr : class_of_bin.data(),
+                                                class_of_bin.size(), n_classes, top_n, top.empty() ? nullptr : top.data(),
+                                                summaries.empty() ? nullptr : summaries.data(), stats);
+    check(rc, "GCSA::kmer_top_classes_batch()");
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).

@@ -939,6 +939,64 @@ int gcsa2_seed_classes_device(const gcsa2_index* index, const uint64_t* d_group_
                               const gcsa2_mem* d_seeds, uint64_t n_seeds, const uint64_t* d_weights /* or NULL = 1 each */,
                               uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
                               uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream);
+/* ---- k-mer top classes: the sparse form of k-mer classes, for any number of classes ---------------------------------------------
+ * A metagenomic binner votes over 10^5 contigs, a taxonomic classifier over 10^4 to 10^5 taxa, a pangenome user over every node:
+ * far beyond GCSA2_CLASS_LIMIT, and a dense row per read does not scale.  What leaves the device here is, per read, the top_n
+ * classes with the most votes and a summary of the row -- no matrix, no hit list.
+ *
+ * DEFINITION.
+ *   - The windows, FOUND, COUNTED, class(v), n_c(R), none(R), classes(R) and the vote x_c of a counted record are exactly those
+ *     of gcsa2_kmer_classes_device; GCSA2_CLASS_PER_WINDOW and GCSA2_CLASS_UNAMBIGUOUS mean the same; votes[q][c] is the same
+ *     64-bit sum.  The only difference: n_classes may be 1 .. 0xFFFFFFFF.  Class ids are < n_classes; GCSA2_CLASS_NONE and any
+ *     id >= n_classes mean "no class", as before.
+ *   - summary(q): voted = the number of classes c with votes[q][c] > 0 (a class whose records all have weight 0 has no vote and
+ *     is not voted); total = the row's sum; counted = the number of counted records of q, unweighted.
+ *   - The top row: order the voted classes by more votes first, the lower id on a tie.  d_top[q top_n + j] for
+ *     j < min(top_n, voted(q)) is the j-th class in that order with its votes; every later entry of the row is
+ *     {GCSA2_UNKNOWN, 0}.
+ *   - Rows and summaries are WRITTEN, not added to: the call writes every entry of d_top[0 .. n_patterns top_n) and of
+ *     d_summaries[0 .. n_patterns), and nothing behind them.
+ *   - stats is gcsa2_class_stats, every field as for gcsa2_kmer_classes_device.
+ *   - d_top, d_summaries and stats may each be NULL; all three NULL is valid and does the work.
+ *   - LAW: for n_classes <= GCSA2_CLASS_LIMIT and equal arguments, d_top[q][0] = {best, best_votes} and d_top[q][1] = {second,
+ *     second_votes} of gcsa2_kmer_classes_device (gcsa2_seed_classes_device for the seed form), total, counted and every field
+ *     of stats are equal, and the whole top row is the sorted non-zero entries of the dense row.
+ *
+ * GCSA2_ERR_INVALID_ARGUMENT, with nothing written (stats included) and before any device is touched: the refusals of
+ * gcsa2_kmer_classes_device with the bound on n_classes replaced by n_classes == 0 or n_classes > 0xFFFFFFFF, and top_n == 0 or
+ * top_n > GCSA2_TOP_LIMIT.  Missing components, the 2^32 limits, the limit of 2^31 values per range, n_bins == 0,
+ * n_patterns == 0 and "enqueued on `stream`, complete on return" are those of gcsa2_kmer_classes_device.
+ *
+ * The search, the cap, the fold, the chunks (GCSA2_SUPPORT_CHUNK) and the locate are those of k-mer classes; the keys are
+ * run << 33 | class with "no class" = 2^32, the signature entries n_c << 32 | class.  Then one wavefront per read adds its
+ * records' signatures into a hash table in LDS (32-bit key, 64-bit counter, open addressing) and keeps the top row in its
+ * registers.  A read that votes for more classes than the table holds is processed again in 2, 4, ... passes over a partition
+ * of the class ids by hash, whose top rows merge and whose voted and total add up: the result is exact whatever the number of
+ * classes.  GCSA2_TOP_SLOTS (a test knob, read per call; a power of two, 64 .. 4096, default 512) is the table's size; no
+ * result depends on it.  No global atomic but three per workgroup for the stats. */
+#define GCSA2_TOP_LIMIT 64                       /* top_n may be 1 .. GCSA2_TOP_LIMIT */
+typedef struct gcsa2_class_vote  { uint64_t class_id, votes; } gcsa2_class_vote;
+typedef struct gcsa2_top_summary { uint64_t voted, total, counted; } gcsa2_top_summary;
+int gcsa2_kmer_top_classes_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                                  uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                                  const uint32_t* d_class_of_bin, uint64_t n_bins, uint64_t n_classes, uint64_t top_n,
+                                  gcsa2_class_vote* d_top /* n_patterns x top_n, row-major, or NULL */,
+                                  gcsa2_top_summary* d_summaries /* n_patterns, or NULL */,
+                                  gcsa2_class_stats* stats /* host, may be NULL */, void* stream);
+/* The same for reads and the class map in host memory, into host arrays: pieces, the map upload, the refusal of offsets that
+ * do not start at 0 or decrease, and stats summed over the pieces are exactly those of gcsa2_kmer_classes_batch. */
+int gcsa2_kmer_top_classes_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                                 uint64_t k, uint64_t stride, uint64_t hit_max, uint64_t shift, int flags,
+                                 const uint32_t* class_of_bin, uint64_t n_bins, uint64_t n_classes, uint64_t top_n,
+                                 gcsa2_class_vote* top /* host, n_patterns x top_n, or NULL */,
+                                 gcsa2_top_summary* summaries /* host, or NULL */, gcsa2_class_stats* stats);
+/* The same over seed records in groups: groups, weights, invalid groups and what stats counts are exactly those of
+ * gcsa2_seed_classes_device.  An invalid group is NOT READ: its row is all {GCSA2_UNKNOWN, 0} and its summary is zero. */
+int gcsa2_seed_top_classes_device(const gcsa2_index* index, const uint64_t* d_group_offsets, uint64_t n_groups,
+                                  const gcsa2_mem* d_seeds, uint64_t n_seeds, const uint64_t* d_weights /* or NULL = 1 each */,
+                                  uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
+                                  uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
+                                  gcsa2_class_stats* stats, void* stream);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
