@@ -2092,22 +2092,6 @@ int gcsa2_locate_into(const gcsa2_index* ix, const uint64_t* d_ranges, uint64_t 
 
 // ---- host-pointer entry points: copy in, run, copy out, synchronise ----------------------
 
-namespace {
-// pattern offsets handed over by a host caller: non-decreasing, or the kernels would read outside the pattern buffer
-inline bool offsets_ok(const uint64_t* offsets, uint64_t nq, u64* longest = nullptr)
-{
-  u64 bad = 0, most = 0;
-  for(u64 q = 0; q < nq; q++)
-  {
-    const u64 len = offsets[q + 1] - offsets[q];
-    bad |= u64(offsets[q + 1] < offsets[q]);
-    most = (len > most ? len : most);
-  }
-  if(longest != nullptr) { *longest = most; }
-  return bad == 0;
-}
-}
-
 } // extern "C"
 
 namespace {
@@ -4843,7 +4827,7 @@ int gcsa2_mem_hits_bounded_batch(const gcsa2_index* ix, const uint8_t* patterns,
   try {   // no C++ exception may cross the C boundary
   DeviceGuard guard(ix->device);
   g_error.clear();
-  const std::vector<u64> cut = (offsets[nq] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, nq} : cut_pieces(offsets, nq, ix->tune.ms_piece_bytes));
+  const std::vector<u64> cut = read_cut(ix, offsets, nq);
   const u64 pieces = cut.size() - 1;
   DBuf<u8> d_pat; DBuf<u64> d_off, d_mem_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_mems;
   u64 mbase = 0, hbase = 0;
@@ -5108,14 +5092,15 @@ int kmer_windows_checks(const gcsa2_index* ix, u64 k, u64 stride, int flags, con
   return GCSA2_OK;
 }
 
-// gcsa2_kmer_windows_device after its argument checks (n_patterns > 0).  One host round trip: the number of windows.
-int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, int flags,
-                      u64* d_window_offsets, gcsa2_kmer_profile* d_profiles, u64* d_ranges, u64* d_counts, u64 capacity, u64* total_windows,
-                      hipStream_t st)
+// How every k-mer call begins: where each read's windows start (n_patterns + 1 entries, in `woff_or_null` or in scratch) and,
+// after one host round trip, their number.  The stream is idle when this returns without a HIP error; a call of 2^32 or
+// more windows is refused in `name`, with `total` set.
+int window_plan(Scratch& scratch, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, u64* woff_or_null, const char* name, hipStream_t st,
+                u64*& woff, u64& total)
 {
-  Scratch scratch(ix, st);
-  u64 *sizes = nullptr, *woff = d_window_offsets;
+  u64* sizes = nullptr;
   char* scan_tmp = nullptr;
+  woff = woff_or_null;
   HIP_TRY(scratch.get(sizes, n_patterns + 1));
   if(woff == nullptr) { HIP_TRY(scratch.get(woff, n_patterns + 1)); }
   hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
@@ -5124,12 +5109,27 @@ int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
   HIP_TRY(scratch.get(scan_tmp, scan_bytes));
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  u64 total = 0;
   HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
+  if(total >= (u64(1) << 32))
+  {
+    scratch.settled = true;
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch");
+  }
+  return GCSA2_OK;
+}
+
+// gcsa2_kmer_windows_device after its argument checks (n_patterns > 0).  One host round trip: the number of windows.
+int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, int flags,
+                      u64* d_window_offsets, gcsa2_kmer_profile* d_profiles, u64* d_ranges, u64* d_counts, u64 capacity, u64* total_windows,
+                      hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *woff = nullptr, total = 0;
+  const int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, d_window_offsets, "kmer_windows", st, woff, total);
   *total_windows = total;
-  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_windows: 2^32 or more windows in one call; split the batch"); }
+  if(rc != GCSA2_OK) { return rc; }
+  scratch.settled = true;
   if((d_ranges != nullptr || d_counts != nullptr) && total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "window buffer too small"); }
   if(d_profiles == nullptr && d_ranges == nullptr && d_counts == nullptr) { return GCSA2_OK; }
   scratch.settled = false;
@@ -5154,6 +5154,54 @@ int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
   }
   HIP_TRY(hipStreamSynchronize(st));
   scratch.settled = true;
+  return GCSA2_OK;
+}
+
+// The k-mer seed search over the windows of window_plan (total > 0): the found windows as seed records with their count()s, in
+// arrival order, in an area of `capacity` records; `m`: how many were found, to which the caller reacts if the area was
+// short.  attempts == 2 (capacity is a caller's guess): a short area is re-made at m and the search runs again, so each
+// run zeroes what it left behind (`prof`, found[spans]) and the area is taken after the owners are on their way; attempts ==
+// 1 (capacity == total): the area first, one run.  One host round trip per run.
+int kmer_seed_search(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
+                     const u64* woff, u64 total, u64 capacity, gcsa2_kmer_profile* prof, int attempts, hipStream_t st, SeedEmit& emit, u64& m)
+{
+  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
+  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
+  u64* owners = nullptr;
+  emit = SeedEmit{};
+  HIP_TRY(scratch.get(owners, spans + 1));
+  HIP_TRY(scratch.get(emit.cursor, 1));
+  HIP_TRY(scratch.get(emit.base, spans));
+  HIP_TRY(scratch.get(emit.found, spans + 1));
+  HIP_TRY(scratch.get(emit.mask, spans));
+  // the reads of every wavefront's first window: the bracket in which a lane looks for its own read
+  auto block_owners = [&]() -> int
+  {
+    scratch.settled = false;
+    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
+    LAUNCH_CHECK("k_block_owners");
+    return GCSA2_OK;
+  };
+  const bool rerun = attempts > 1;
+  if(rerun) { const int rc = block_owners(); if(rc != GCSA2_OK) { return rc; } }
+  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
+  emit.capacity = capacity;
+  for(int attempt = 0; attempt < attempts; attempt++)
+  {
+    HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
+    HIP_TRY(scratch.get(emit.counts, emit.capacity));
+    if(!rerun) { const int rc = block_owners(); if(rc != GCSA2_OK) { return rc; } }
+    HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
+    if(rerun) { HIP_TRY(hipMemsetAsync(emit.found + spans, 0, sizeof(u32), st)); }
+    if(prof != nullptr) { HIP_TRY(hipMemsetAsync(prof, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
+    if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
+    else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
+    LAUNCH_CHECK("k_kmer_seeds");
+    HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if(m <= emit.capacity) { break; }
+    if(attempt + 1 < attempts) { emit.capacity = m; }        // the records are still needed, for the totals
+  }
   return GCSA2_OK;
 }
 
@@ -5189,11 +5237,10 @@ int gcsa2_kmer_windows_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
 }
 
 // The host form.  The window offsets are a function of the pattern offsets alone, so they -- and the total, and the refusal of
-// a short buffer -- are worked out here before any device work.  A batch of two pieces' worth of pattern bytes or more is cut
-// into pieces of reads (tune.ms_piece_bytes, cut_pieces) that tune.ms_threads host threads carry: reads and their rebased
-// offsets in, gcsa2_kmer_windows_device with the window offsets left in scratch, then the piece's profiles / ranges / counts
-// out to their places in the caller's arrays, which the host-side offsets name.  With profiles as the only output that is
-// the reads in and 32 bytes per read out.
+// a short buffer -- are worked out here before any device work.  A piece (for_read_pieces) travels through a Lease, which
+// brings its own stream: reads and their rebased offsets in, gcsa2_kmer_windows_device with the window offsets left in
+// scratch, then the piece's profiles / ranges / counts out to their places in the caller's arrays, which the host-side
+// offsets name.  With profiles as the only output that is the reads in and 32 bytes per read out.
 int gcsa2_kmer_windows_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
                              uint64_t stride, int flags, uint64_t* window_offsets, gcsa2_kmer_profile* profiles, uint64_t* ranges,
                              uint64_t* counts, uint64_t capacity, uint64_t* total_windows)
@@ -5203,57 +5250,40 @@ int gcsa2_kmer_windows_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   *total_windows = 0;
   if(n_patterns == 0) { if(window_offsets != nullptr) { window_offsets[0] = 0; } return GCSA2_OK; }
   if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
-  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
-  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
   std::vector<u64> woff(n_patterns + 1);
-  u64 total = 0;
-  for(u64 q = 0; q < n_patterns; q++)
-  {
-    const u64 len = offsets[q + 1] - offsets[q];
-    woff[q] = total;
-    if(len >= k) { total += (len - k) / stride + 1; }
-  }
-  woff[n_patterns] = total;
+  const u64 total = host_windows(offsets, n_patterns, k, stride, woff.data());
   *total_windows = total;
   if((ranges != nullptr || counts != nullptr) && total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "window buffer too small"); }
   if(window_offsets != nullptr) { std::memcpy(window_offsets, woff.data(), (n_patterns + 1) * sizeof(u64)); }
   if(profiles == nullptr && ranges == nullptr && counts == nullptr) { return GCSA2_OK; }
-  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
-                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
-  const u64 pieces = cut.size() - 1;
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  return fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  return for_read_pieces(ix, offsets, read_cut(ix, offsets, n_patterns), [&](const ReadPiece& p, Outcome& out) -> bool
   {
-    DeviceGuard guard(ix->device);
-    std::vector<u64> local;
-    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      const u64 at = woff[b], windows = woff[b + count] - at;
-      rebase_piece(offsets, b, count, local);
-      Lease lease(ix);
-      hipError_t e = lease.begin(Lease::need(bytes + 16) + Lease::need((count + 1) * 8) + (profiles != nullptr ? Lease::need(count * 32) : 0) +
-                                 (ranges != nullptr ? Lease::need(windows * 16) : 0) + (counts != nullptr ? Lease::need(windows * 8) : 0));
-      if(e != hipSuccess) { out.set(GCSA2_ERR_OUT_OF_MEMORY, std::string("staging of a piece: ") + hipGetErrorString(e)); break; }
-      u8* d_pat = lease.dev<u8>(bytes + 16); u64* d_off = lease.dev<u64>(count + 1);
-      gcsa2_kmer_profile* d_prof = (profiles != nullptr ? lease.dev<gcsa2_kmer_profile>(count) : nullptr);
-      u64* d_rng = (ranges != nullptr ? lease.dev<u64>(2 * windows) : nullptr);
-      u64* d_cnt = (counts != nullptr ? lease.dev<u64>(windows) : nullptr);
-      e = lease.up(d_pat, patterns + first, bytes);
-      if(e == hipSuccess) { e = lease.up(d_off, local.data(), (count + 1) * sizeof(u64)); }
-      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      u64 got = 0;
-      const int piece_rc = gcsa2_kmer_windows_device(ix, d_pat, d_off, count, k, stride, flags, nullptr, d_prof, d_rng, d_cnt, windows, &got, lease.stream());
-      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-      if(profiles != nullptr) { e = lease.down(profiles + b, d_prof, count * sizeof(gcsa2_kmer_profile)); }
-      if(e == hipSuccess && ranges != nullptr) { e = lease.down(ranges + 2 * at, d_rng, 2 * windows * sizeof(u64)); }
-      if(e == hipSuccess && counts != nullptr) { e = lease.down(counts + at, d_cnt, windows * sizeof(u64)); }
-      if(e == hipSuccess) { e = lease.finish(); }
-      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
-    }
-  });
+    const u64 at = woff[p.b], windows = woff[p.b + p.count] - at;
+    Lease lease(ix);
+    hipError_t e = lease.begin(Lease::need(p.bytes + 16) + Lease::need((p.count + 1) * 8) + (profiles != nullptr ? Lease::need(p.count * 32) : 0) +
+                               (ranges != nullptr ? Lease::need(windows * 16) : 0) + (counts != nullptr ? Lease::need(windows * 8) : 0));
+    if(e != hipSuccess) { out.set(GCSA2_ERR_OUT_OF_MEMORY, std::string("staging of a piece: ") + hipGetErrorString(e)); return false; }
+    u8* d_pat = lease.dev<u8>(p.bytes + 16); u64* d_off = lease.dev<u64>(p.count + 1);
+    gcsa2_kmer_profile* d_prof = (profiles != nullptr ? lease.dev<gcsa2_kmer_profile>(p.count) : nullptr);
+    u64* d_rng = (ranges != nullptr ? lease.dev<u64>(2 * windows) : nullptr);
+    u64* d_cnt = (counts != nullptr ? lease.dev<u64>(windows) : nullptr);
+    e = lease.up(d_pat, patterns + p.first, p.bytes);
+    if(e == hipSuccess) { e = lease.up(d_off, p.local, (p.count + 1) * sizeof(u64)); }
+    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+    u64 got = 0;
+    const int piece_rc = gcsa2_kmer_windows_device(ix, d_pat, d_off, p.count, k, stride, flags, nullptr, d_prof, d_rng, d_cnt, windows, &got, lease.stream());
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    if(profiles != nullptr) { e = lease.down(profiles + p.b, d_prof, p.count * sizeof(gcsa2_kmer_profile)); }
+    if(e == hipSuccess && ranges != nullptr) { e = lease.down(ranges + 2 * at, d_rng, 2 * windows * sizeof(u64)); }
+    if(e == hipSuccess && counts != nullptr) { e = lease.down(counts + at, d_cnt, windows * sizeof(u64)); }
+    if(e == hipSuccess) { e = lease.finish(); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    return true;
+  }, false);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_windows_batch: ") + e.what()); }
 }
 
@@ -5285,20 +5315,9 @@ int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint6
                    u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
 {
   Scratch scratch(ix, st);
-  u64 *sizes = nullptr, *woff = nullptr;
-  char* scan_tmp = nullptr;
-  HIP_TRY(scratch.get(sizes, n_patterns + 1));
-  HIP_TRY(scratch.get(woff, n_patterns + 1));
-  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
-  LAUNCH_CHECK("k_window_counts");
-  size_t scan_bytes = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  u64 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if(total >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more windows in one call; split the batch"); }
+  u64 *woff = nullptr, total = 0;
+  int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_hits", st, woff, total);
+  if(rc != GCSA2_OK) { return rc; }
   // no seed: zeroed offsets, the profiles are their window numbers
   auto nothing_found = [&](const gcsa2_kmer_profile* prof) -> int
   {
@@ -5316,41 +5335,19 @@ int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint6
   if(total == 0) { return nothing_found(nullptr); }
   // 1. the search: seed records in arrival order, the profiles in scratch
   const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
-  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
-  u64* owners = nullptr;
   gcsa2_kmer_profile* prof = nullptr;
   SeedEmit emit{};
-  HIP_TRY(scratch.get(owners, spans + 1));
-  HIP_TRY(scratch.get(emit.cursor, 1));
-  HIP_TRY(scratch.get(emit.base, spans));
-  HIP_TRY(scratch.get(emit.found, spans + 1));
-  HIP_TRY(scratch.get(emit.mask, spans));
-  if(d_profiles != nullptr) { HIP_TRY(scratch.get(prof, n_patterns)); }
-  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
-  LAUNCH_CHECK("k_block_owners");
-  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
   u64 m = 0;
-  emit.capacity = std::min(seed_capacity, total);
-  for(int attempt = 0; attempt < 2; attempt++)
-  {
-    HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
-    HIP_TRY(scratch.get(emit.counts, emit.capacity));
-    HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(emit.found + spans, 0, sizeof(u32), st));
-    if(prof != nullptr) { HIP_TRY(hipMemsetAsync(prof, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
-    if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
-    else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
-    LAUNCH_CHECK("k_kmer_seeds");
-    HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if(m <= emit.capacity || attempt == 1) { break; }
-    emit.capacity = m;        // the caller's capacity is short: the records are still needed, for *total_hits
-  }
+  if(d_profiles != nullptr) { HIP_TRY(scratch.get(prof, n_patterns)); }
+  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, std::min(seed_capacity, total), prof, 2, st, emit, m);
+  if(rc != GCSA2_OK) { return rc; }
   if(m > emit.capacity) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "kmer_hits: two runs of the search disagree on the number of seeds"); }
   *total_seeds = m;
   if(m == 0) { return nothing_found(prof); }
   // 2. window order: the scan of the wavefronts' found numbers, then every wavefront's records to their place
   u64 *recs = nullptr, *counts = nullptr;
+  size_t scan_bytes = 0;
+  char* scan_tmp = nullptr;
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, emit.found, emit.found, size_t(spans + 1), st));
   HIP_TRY(scratch.get(scan_tmp, scan_bytes));
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, emit.found, emit.found, size_t(spans + 1), st));
@@ -5359,7 +5356,7 @@ int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint6
   hipLaunchKernelGGL(k_seed_place, dim3(grid_for(spans * 64)), dim3(TPB), 0, st, emit.base, emit.found, spans, emit.recs, emit.counts, recs, counts);
   LAUNCH_CHECK("k_seed_place");
   // 3. count class, locate, hits in seed order (mem_hits' tail); offsets and profiles only once everything fits
-  const int rc = mem_hits_tail(ix, recs, counts, m, hit_max, over, d_seeds, seed_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
+  rc = mem_hits_tail(ix, recs, counts, m, hit_max, over, d_seeds, seed_capacity, d_hit_offsets, d_hits, hit_capacity, total_hits, scratch, st);
   if(rc != GCSA2_OK) { return rc; }
   scratch.settled = false;
   hipLaunchKernelGGL(k_seed_offsets, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, woff, n_patterns, total, spans, emit.found, emit.mask, d_seed_offsets);
@@ -5405,11 +5402,8 @@ int gcsa2_kmer_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, con
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_device: ") + e.what()); }
 }
 
-// The host form.  One piece: copied in, run on device buffers of the caller's capacities, copied out only when everything fits.
-// A batch of two pieces' worth of read bytes or more is cut into pieces of whole reads (tune.ms_piece_bytes, cut_pieces) that
-// tune.ms_threads host threads carry; the number of seeds of a piece is not known before it ran, so every piece keeps its four
-// arrays in host memory (sized from a first refusal of the device form) and the caller's arrays are put together from them in
-// read order at the end, when the totals are known to fit.
+// The host form (seed_pieces_batch).  Its own: the window count refused before any device work, a first run with room for
+// every window, and the profiles as the per-read output.
 int gcsa2_kmer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
                           uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles, uint64_t* seed_offsets,
                           gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* hit_offsets, uint64_t* hits,
@@ -5426,93 +5420,26 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const 
   }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more reads in one call; split the batch"); }
   if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
-  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
-  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
-  u64 windows_all = 0;
-  for(u64 q = 0; q < n_patterns; q++)
+  if(host_windows(offsets, n_patterns, k, stride) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more windows in one call; split the batch"); }
+  // several pieces: room for every window, so that the search runs once, and an estimate of the hits
+  auto estimate = [&](const ReadPiece& p) -> std::pair<u64, u64>
   {
-    const u64 len = offsets[q + 1] - offsets[q];
-    if(len >= k) { windows_all += (len - k) / stride + 1; }
-  }
-  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_hits: 2^32 or more windows in one call; split the batch"); }
-  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
-                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
-  const u64 pieces = cut.size() - 1;
-  struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
-  std::vector<Piece> done(pieces);
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+    const u64 windows = host_windows(p.local, p.count, k, stride);
+    if(p.pieces == 1) { return {std::min(seed_capacity, windows), hit_capacity}; }
+    return {windows, 4 * windows};
+  };
+  auto run = [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, u8* d_prof, u64* d_seed_off, gcsa2_mem* d_seeds, u64 rm, u64* m, u64* d_hit_off,
+                 u64* d_hits, u64 rh, u64* h) -> int
   {
-    DeviceGuard guard(ix->device);
-    std::vector<u64> local;
-    hipStream_t stream = nullptr;
-    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
-    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      rebase_piece(offsets, b, count, local);
-      u64 windows = 0;
-      for(u64 q = 0; q < count; q++) { const u64 len = local[q + 1] - local[q]; if(len >= k) { windows += (len - k) / stride + 1; } }
-      Piece& piece = done[c];
-      DBuf<u8> d_pat; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds; DBuf<gcsa2_kmer_profile> d_prof;
-      hipError_t e = d_pat.alloc(bytes + 16);
-      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
-      if(e == hipSuccess) { e = d_seed_off.alloc(count + 1); }
-      if(e == hipSuccess && profiles != nullptr) { e = d_prof.alloc(count); }
-      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
-      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      // one piece: the caller's capacities (a refusal is the call's); several: room for every window, so that the search runs
-      // once, and an estimate of the hits, then what the refusal asks for
-      u64 rm = (pieces == 1 ? std::min(seed_capacity, windows) : windows), rh = (pieces == 1 ? hit_capacity : 4 * rm);
-      int piece_rc = GCSA2_OK;
-      for(int attempt = 0; attempt < 2; attempt++)
-      {
-        d_seeds.release(); d_hit_off.release(); d_hits.release();
-        e = d_seeds.alloc(rm);
-        if(e == hipSuccess) { e = d_hit_off.alloc(rm + 1); }
-        if(e == hipSuccess) { e = d_hits.alloc(rh); }
-        if(e != hipSuccess) { break; }
-        piece_rc = gcsa2_kmer_hits_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, over, d_prof.p, d_seed_off.p, d_seeds.p, rm, &piece.m,
-                                          d_hit_off.p, d_hits.p, rh, &piece.h, stream);
-        if(piece_rc == GCSA2_ERR_BUFFER_TOO_SMALL && pieces > 1 && attempt == 0 && (piece.m > rm || piece.h > rh)) { rm = piece.m; rh = piece.h; continue; }
-        break;
-      }
-      if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); break; }
-      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-      piece.seed_off.resize(count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
-      e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
-      if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess && profiles != nullptr) { e = hipMemcpy(profiles + b, d_prof.p, count * sizeof(gcsa2_kmer_profile), hipMemcpyDeviceToHost); }
-      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
-    }
-    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
-  });
-  u64 m = 0, h = 0;
-  for(const Piece& piece : done) { m += piece.m; h += piece.h; }
-  *total_seeds = m;
-  *total_hits = h;
-  if(rc != GCSA2_OK) { return rc; }
-  if(m > seed_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed buffer too small"); }
-  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
-  u64 mbase = 0, hbase = 0;
-  for(u64 c = 0; c < pieces; c++)
-  {
-    const Piece& piece = done[c];
-    const u64 b = cut[c], count = cut[c + 1] - b;
-    for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
-    if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
-    for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }
-    if(piece.h > 0) { std::memcpy(hits + hbase, piece.hits.data(), piece.h * sizeof(u64)); }
-    mbase += piece.m;
-    hbase += piece.h;
-  }
-  return GCSA2_OK;
+    return gcsa2_kmer_hits_device(ix, d_pat, d_off, p.count, k, stride, hit_max, over, reinterpret_cast<gcsa2_kmer_profile*>(d_prof), d_seed_off, d_seeds, rm, m,
+                                  d_hit_off, d_hits, rh, h, p.stream);
+  };
+  return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, sizeof(gcsa2_kmer_profile), profiles, seed_offsets, seeds, seed_capacity,
+                           total_seeds, hit_offsets, hits, hit_capacity, total_hits);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_batch: ") + e.what()); }
 }
 
@@ -5634,11 +5561,8 @@ int gcsa2_capped_seeds_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_capped_seeds_device: ") + e.what()); }
 }
 
-// The host form.  One piece: copied in, run on device buffers of the caller's capacities, copied out only when everything fits.
-// A batch of two pieces' worth of read bytes or more is cut into pieces of whole reads (tune.ms_piece_bytes, cut_pieces) that
-// tune.ms_threads host threads carry, as gcsa2_kmer_hits_batch: every piece keeps its four arrays in host memory (sized from a
-// first refusal of the device form, whose sizing run keeps no records) and the caller's arrays are put together from them in
-// read order at the end, when the totals are known to fit.
+// The host form (seed_pieces_batch).  Its own: the first run of a piece among several is a guess, and a refusal costs
+// little, because the device form's sizing run keeps no records.
 int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t min_length,
                              uint64_t max_length, uint64_t max_count, uint64_t hit_max, int over, uint64_t* seed_offsets, gcsa2_mem* seeds,
                              uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity,
@@ -5655,83 +5579,25 @@ int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "capped_seeds: 2^32 or more reads in one call; split the batch"); }
   if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
-  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
-  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer"); }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
-  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
-                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
-  const u64 pieces = cut.size() - 1;
-  struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
-  std::vector<Piece> done(pieces);
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  // one piece: never more seeds than a read has positions for; several: one seed per eight positions, four hits per seed
+  auto estimate = [&](const ReadPiece& p) -> std::pair<u64, u64>
   {
-    DeviceGuard guard(ix->device);
-    std::vector<u64> local;
-    hipStream_t stream = nullptr;
-    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
-    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      rebase_piece(offsets, b, count, local);
-      Piece& piece = done[c];
-      DBuf<u8> d_pat; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds;
-      hipError_t e = d_pat.alloc(bytes + 16);
-      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
-      if(e == hipSuccess) { e = d_seed_off.alloc(count + 1); }
-      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
-      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      // one piece: the caller's capacities, never more seeds than a read has positions for (a refusal is the call's);
-      // several: an estimate, then what the refusal asks for
-      u64 rm = (pieces == 1 ? std::min(seed_capacity, bytes / min_length) : bytes / (8 * min_length) + count + 1);
-      u64 rh = (pieces == 1 ? hit_capacity : 4 * rm);
-      int piece_rc = GCSA2_OK;
-      for(int attempt = 0; attempt < 2; attempt++)
-      {
-        d_seeds.release(); d_hit_off.release(); d_hits.release();
-        e = d_seeds.alloc(rm);
-        if(e == hipSuccess) { e = d_hit_off.alloc(rm + 1); }
-        if(e == hipSuccess) { e = d_hits.alloc(rh); }
-        if(e != hipSuccess) { break; }
-        piece_rc = gcsa2_capped_seeds_device(ix, d_pat.p, d_off.p, count, min_length, max_length, max_count, hit_max, over, d_seed_off.p, d_seeds.p, rm,
-                                             &piece.m, d_hit_off.p, d_hits.p, rh, &piece.h, stream);
-        if(piece_rc == GCSA2_ERR_BUFFER_TOO_SMALL && pieces > 1 && attempt == 0 && (piece.m > rm || piece.h > rh)) { rm = piece.m; rh = piece.h; continue; }
-        break;
-      }
-      if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); break; }
-      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-      piece.seed_off.resize(count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
-      e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
-      if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
-      if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
-      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
-    }
-    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
-  });
-  u64 m = 0, h = 0;
-  for(const Piece& piece : done) { m += piece.m; h += piece.h; }
-  *total_seeds = m;
-  *total_hits = h;
-  if(rc != GCSA2_OK) { return rc; }
-  if(m > seed_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed buffer too small"); }
-  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
-  u64 mbase = 0, hbase = 0;
-  for(u64 c = 0; c < pieces; c++)
+    if(p.pieces == 1) { return {std::min(seed_capacity, p.bytes / min_length), hit_capacity}; }
+    const u64 rm = p.bytes / (8 * min_length) + p.count + 1;
+    return {rm, 4 * rm};
+  };
+  auto run = [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, u8*, u64* d_seed_off, gcsa2_mem* d_seeds, u64 rm, u64* m, u64* d_hit_off, u64* d_hits,
+                 u64 rh, u64* h) -> int
   {
-    const Piece& piece = done[c];
-    const u64 b = cut[c], count = cut[c + 1] - b;
-    for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
-    if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
-    for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }
-    if(piece.h > 0) { std::memcpy(hits + hbase, piece.hits.data(), piece.h * sizeof(u64)); }
-    mbase += piece.m;
-    hbase += piece.h;
-  }
-  return GCSA2_OK;
+    return gcsa2_capped_seeds_device(ix, d_pat, d_off, p.count, min_length, max_length, max_count, hit_max, over, d_seed_off, d_seeds, rm, m, d_hit_off, d_hits,
+                                     rh, h, p.stream);
+  };
+  return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, 0, nullptr, seed_offsets, seeds, seed_capacity, total_seeds, hit_offsets, hits,
+                           hit_capacity, total_hits);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_capped_seeds_batch: ") + e.what()); }
 }
 
@@ -5889,47 +5755,15 @@ int kmer_support_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
                       u64 shift, int flags, u64* d_support, u64 n_bins, gcsa2_support_stats* st_out, hipStream_t st)
 {
   Scratch scratch(ix, st);
-  u64 *sizes = nullptr, *woff = nullptr;
-  char* scan_tmp = nullptr;
-  HIP_TRY(scratch.get(sizes, n_patterns + 1));
-  HIP_TRY(scratch.get(woff, n_patterns + 1));
-  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
-  LAUNCH_CHECK("k_window_counts");
-  size_t scan_bytes = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  u64 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  u64 *woff = nullptr, total = 0, m = 0;
+  int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_support", st, woff, total);
+  if(rc != GCSA2_OK) { return rc; }
   scratch.settled = true;
-  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more windows in one call; split the batch"); }
   st_out->windows = total;
   if(total == 0) { return GCSA2_OK; }
-  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
-  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
-  u64* owners = nullptr;
   SeedEmit emit{};
-  HIP_TRY(scratch.get(owners, spans + 1));
-  HIP_TRY(scratch.get(emit.cursor, 1));
-  HIP_TRY(scratch.get(emit.base, spans));
-  HIP_TRY(scratch.get(emit.found, spans + 1));
-  HIP_TRY(scratch.get(emit.mask, spans));
-  emit.capacity = total;
-  HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
-  HIP_TRY(scratch.get(emit.counts, emit.capacity));
-  scratch.settled = false;
-  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
-  LAUNCH_CHECK("k_block_owners");
-  HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
-  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
-  gcsa2_kmer_profile* const no_profiles = nullptr;
-  if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
-  else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
-  LAUNCH_CHECK("k_kmer_seeds");
-  u64 m = 0;
-  HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, total, nullptr, 1, st, emit, m);
+  if(rc != GCSA2_OK) { return rc; }
   scratch.settled = true;
   if(m > emit.capacity) { return fail(GCSA2_ERR_HIP, "kmer_support: more seeds than windows"); }
   if(m == 0) { return GCSA2_OK; }
@@ -5984,9 +5818,9 @@ int gcsa2_seed_support_device(const gcsa2_index* ix, const gcsa2_mem* d_seeds, u
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_support_device: ") + e.what()); }
 }
 
-// The host form.  One zeroed device array of n_bins for the whole call; the reads travel in pieces of whole reads
-// (tune.ms_piece_bytes, cut_pieces) on tune.ms_threads host threads, each piece one gcsa2_kmer_support_device on its thread's
-// stream -- the pieces add into the one array with atomics -- and the array is added into the caller's at the end.
+// The host form.  One zeroed device array of n_bins for the whole call; each piece (for_read_pieces) is one
+// gcsa2_kmer_support_device on its thread's stream -- the pieces add into the one array with atomics -- and the array is
+// added into the caller's at the end.
 int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
                              uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, uint64_t* support, uint64_t n_bins,
                              gcsa2_support_stats* stats)
@@ -5997,47 +5831,24 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   gcsa2_support_stats sums{};
   if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
   if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: offsets is NULL"); }
-  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
-  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: patterns is NULL"); }
+  rc = reads_ok(patterns, offsets, n_patterns, "kmer_support");
+  if(rc != GCSA2_OK) { return rc; }
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
-  u64 windows_all = 0;
-  for(u64 q = 0; q < n_patterns; q++)
-  {
-    const u64 len = offsets[q + 1] - offsets[q];
-    if(len >= k) { windows_all += (len - k) / stride + 1; }
-  }
-  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more windows in one call; split the batch"); }
+  if(host_windows(offsets, n_patterns, k, stride) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more windows in one call; split the batch"); }
   DeviceGuard guard(ix->device);
   DBuf<u64> d_sup;
   HIP_TRY(d_sup.alloc(n_bins));
   HIP_TRY(hipMemset(d_sup.p, 0, (n_bins > 0 ? n_bins : 1) * sizeof(u64)));
-  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
-                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
-  const u64 pieces = cut.size() - 1;
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  std::vector<gcsa2_support_stats> done(pieces);
-  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  std::vector<gcsa2_support_stats> done(cut.size() - 1);
+  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
   {
-    DeviceGuard piece_guard(ix->device);
-    std::vector<u64> local;
-    hipStream_t stream = nullptr;
-    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
-    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      rebase_piece(offsets, b, count, local);
-      DBuf<u8> d_pat; DBuf<u64> d_off;
-      hipError_t e = d_pat.alloc(bytes + 16);
-      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
-      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
-      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      const int piece_rc = gcsa2_kmer_support_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_sup.p, n_bins, &done[c], stream);
-      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-    }
-    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+    DBuf<u8> d_pat; DBuf<u64> d_off;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    const int piece_rc = gcsa2_kmer_support_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, shift, flags, d_sup.p, n_bins, &done[p.c], p.stream);
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    return true;
   });
   if(rc != GCSA2_OK) { return rc; }
   for(const gcsa2_support_stats& s : done)
@@ -6290,55 +6101,70 @@ int kmer_classes_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
                       const ClassesJob& job, gcsa2_class_stats* st_out, hipStream_t st)
 {
   Scratch scratch(ix, st);
-  u64 *sizes = nullptr, *woff = nullptr;
-  char* scan_tmp = nullptr;
-  HIP_TRY(scratch.get(sizes, n_patterns + 1));
-  HIP_TRY(scratch.get(woff, n_patterns + 1));
-  hipLaunchKernelGGL(k_window_counts, dim3(grid_for(n_patterns + 1)), dim3(TPB), 0, st, d_offsets, n_patterns, k, stride, sizes);
-  LAUNCH_CHECK("k_window_counts");
-  size_t scan_bytes = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, woff, size_t(n_patterns + 1), st));
-  u64 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, woff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  u64 *woff = nullptr, total = 0, m = 0;
+  int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_classes", st, woff, total);
+  if(rc != GCSA2_OK) { return rc; }
   scratch.settled = true;
-  if(total >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more windows in one call; split the batch"); }
   st_out->windows = total;
   if(total == 0) { return classes_tail(ix, nullptr, 4, nullptr, nullptr, 0, true, woff, n_patterns, 0, nullptr, nullptr, job, st_out, scratch, st); }
-  const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
-  static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
-  u64* owners = nullptr;
   SeedEmit emit{};
-  HIP_TRY(scratch.get(owners, spans + 1));
-  HIP_TRY(scratch.get(emit.cursor, 1));
-  HIP_TRY(scratch.get(emit.base, spans));
-  HIP_TRY(scratch.get(emit.found, spans + 1));
-  HIP_TRY(scratch.get(emit.mask, spans));
-  emit.capacity = total;
-  HIP_TRY(scratch.get(emit.recs, 4 * emit.capacity));
-  HIP_TRY(scratch.get(emit.counts, emit.capacity));
-  scratch.settled = false;
-  hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, woff, n_patterns, total, OWNER_SPAN, spans, owners);
-  LAUNCH_CHECK("k_block_owners");
-  HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
-  const dim3 grid(unsigned((total + TPB2 - 1) / TPB2));
-  gcsa2_kmer_profile* const no_profiles = nullptr;
-  if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
-  else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, no_profiles, emit); }
-  LAUNCH_CHECK("k_kmer_seeds");
-  u64 m = 0;
-  HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, total, nullptr, 1, st, emit, m);
+  if(rc != GCSA2_OK) { return rc; }
   scratch.settled = true;
   if(m > emit.capacity) { return fail(GCSA2_ERR_HIP, "kmer_classes: more seeds than windows"); }
   return classes_tail(ix, emit.recs, 4, emit.counts, nullptr, m, true, woff, n_patterns, total, emit.base, emit.mask, job, st_out, scratch, st);
 }
 
-// The host form.  The class map goes to the device once; the reads travel in pieces of whole reads (tune.ms_piece_bytes,
-// cut_pieces) on tune.ms_threads host threads, each piece one gcsa2_kmer_classes_device on its thread's stream into device
-// rows and calls of its own, which are copied to the piece's place in the caller's arrays: a row belongs to one read.
+// gcsa2_kmer_classes_device and gcsa2_kmer_top_classes_device: `job` says which, `name` is the call's in its messages
+int kmer_classes_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, const ClassesJob& job,
+                       bool sparse, const char* name, gcsa2_class_stats* stats, void* stream)
+{
+  int rc = kmer_classes_checks(ix, k, stride, job.shift, job.flags, job.class_of_bin, job.n_bins, job.n_classes, "d_class_of_bin", job.top_n, sparse);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+}
+
+// gcsa2_seed_classes_device and gcsa2_seed_top_classes_device, likewise
+int seed_classes_entry(const gcsa2_index* ix, const uint64_t* d_group_offsets, u64 n_groups, const gcsa2_mem* d_seeds, u64 n_seeds, const uint64_t* d_weights,
+                       const ClassesJob& job, bool sparse, const char* name, gcsa2_class_stats* stats, void* stream)
+{
+  int rc = classes_checks(ix, job.shift, job.flags, job.class_of_bin, job.n_bins, job.n_classes, "d_class_of_bin", job.top_n, sparse);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_seeds is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more seeds in one call; split the batch"); }
+  gcsa2_class_stats sums{};
+  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.windows = n_seeds;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  {
+    Scratch scratch(ix, st);
+    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
+                      job, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+}
+
+// The host form.  The class map goes to the device once; each piece (for_read_pieces) is one gcsa2_kmer_classes_device on its
+// thread's stream into device rows and calls of its own, which are copied to the piece's place in the caller's arrays: a row
+// belongs to one read.
 // Both host forms: the dense one (top_n == 0: rows = votes, n_classes u64 per read; records = calls) and the sparse one (rows =
 // top, top_n gcsa2_class_vote per read; records = summaries).
 int classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max, u64 shift,
@@ -6351,60 +6177,36 @@ int classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t
   gcsa2_class_stats sums{};
   if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
   if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: offsets is NULL"); }
-  if(offsets[0] != 0 || !offsets_ok(offsets, n_patterns)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
-  if(patterns == nullptr && offsets[n_patterns] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: patterns is NULL"); }
+  rc = reads_ok(patterns, offsets, n_patterns, "kmer_classes");
+  if(rc != GCSA2_OK) { return rc; }
   const u64 row_bytes = (sparse ? top_n * sizeof(gcsa2_class_vote) : n_classes * sizeof(u64));
   const u64 record_bytes = (sparse ? sizeof(gcsa2_top_summary) : sizeof(gcsa2_class_call));
   try {   // no C++ exception may cross the C boundary
   g_error.clear();
-  u64 windows_all = 0;
-  for(u64 q = 0; q < n_patterns; q++)
-  {
-    const u64 len = offsets[q + 1] - offsets[q];
-    if(len >= k) { windows_all += (len - k) / stride + 1; }
-  }
-  if(windows_all >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more windows in one call; split the batch"); }
+  if(host_windows(offsets, n_patterns, k, stride) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more windows in one call; split the batch"); }
   DeviceGuard guard(ix->device);
   DBuf<u32> d_map;
   HIP_TRY(d_map.alloc(n_bins));
   if(n_bins > 0) { HIP_TRY(hipMemcpy(d_map.p, class_of_bin, n_bins * sizeof(u32), hipMemcpyHostToDevice)); }
-  const std::vector<u64> cut = (offsets[n_patterns] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n_patterns}
-                                                                                   : cut_pieces(offsets, n_patterns, ix->tune.ms_piece_bytes));
-  const u64 pieces = cut.size() - 1;
-  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
-  std::vector<gcsa2_class_stats> done(pieces);
-  rc = fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  std::vector<gcsa2_class_stats> done(cut.size() - 1);
+  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
   {
-    DeviceGuard piece_guard(ix->device);
-    std::vector<u64> local;
-    hipStream_t stream = nullptr;
-    if(pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
-    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
-    {
-      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
-      rebase_piece(offsets, b, count, local);
-      DBuf<u8> d_pat, d_rows, d_records; DBuf<u64> d_off;
-      hipError_t e = d_pat.alloc(bytes + 16);
-      if(e == hipSuccess) { e = d_off.alloc(count + 1); }
-      if(e == hipSuccess && rows != nullptr) { e = d_rows.alloc(count * row_bytes); }
-      if(e == hipSuccess && records != nullptr) { e = d_records.alloc(count * record_bytes); }
-      if(e == hipSuccess && bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + first, bytes, hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, local.data(), (count + 1) * sizeof(u64), hipMemcpyHostToDevice, stream); }
-      if(e == hipSuccess) { e = hipStreamSynchronize(stream); }
-      if(e != hipSuccess) { out.hip_error("upload of a piece", e); break; }
-      void* const piece_rows = (rows != nullptr ? d_rows.p : nullptr);
-      void* const piece_records = (records != nullptr ? d_records.p : nullptr);
-      const int piece_rc = (sparse ? gcsa2_kmer_top_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes, top_n,
-                                                                   static_cast<gcsa2_class_vote*>(piece_rows), static_cast<gcsa2_top_summary*>(piece_records),
-                                                                   &done[c], stream)
-                                   : gcsa2_kmer_classes_device(ix, d_pat.p, d_off.p, count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes,
-                                                               static_cast<u64*>(piece_rows), static_cast<gcsa2_class_call*>(piece_records), &done[c], stream));
-      if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); break; }
-      if(rows != nullptr) { e = hipMemcpy(static_cast<u8*>(rows) + b * row_bytes, d_rows.p, count * row_bytes, hipMemcpyDeviceToHost); }
-      if(e == hipSuccess && records != nullptr) { e = hipMemcpy(static_cast<u8*>(records) + b * record_bytes, d_records.p, count * record_bytes, hipMemcpyDeviceToHost); }
-      if(e != hipSuccess) { out.hip_error("download of a piece", e); break; }
-    }
-    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+    DBuf<u8> d_pat, d_rows, d_records; DBuf<u64> d_off;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    hipError_t e = (rows != nullptr ? d_rows.alloc(p.count * row_bytes) : hipSuccess);
+    if(e == hipSuccess && records != nullptr) { e = d_records.alloc(p.count * record_bytes); }
+    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+    const int piece_rc = (sparse ? gcsa2_kmer_top_classes_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes, top_n,
+                                                                 reinterpret_cast<gcsa2_class_vote*>(d_rows.p), reinterpret_cast<gcsa2_top_summary*>(d_records.p),
+                                                                 &done[p.c], p.stream)
+                                 : gcsa2_kmer_classes_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, shift, flags, d_map.p, n_bins, n_classes,
+                                                             reinterpret_cast<u64*>(d_rows.p), reinterpret_cast<gcsa2_class_call*>(d_records.p), &done[p.c], p.stream));
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    if(rows != nullptr) { e = hipMemcpy(static_cast<u8*>(rows) + p.b * row_bytes, d_rows.p, p.count * row_bytes, hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && records != nullptr) { e = hipMemcpy(static_cast<u8*>(records) + p.b * record_bytes, d_records.p, p.count * record_bytes, hipMemcpyDeviceToHost); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    return true;
   });
   if(rc != GCSA2_OK) { return rc; }
   for(const gcsa2_class_stats& s : done)
@@ -6425,20 +6227,8 @@ int gcsa2_kmer_classes_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
                               uint64_t stride, uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
                               uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats, void* stream)
 {
-  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_classes: d_offsets is NULL"); }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_classes: 2^32 or more reads in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
   const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls, 0, nullptr, nullptr};
-  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_classes_device: ") + e.what()); }
+  return kmer_classes_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, job, false, "kmer_classes", stats, stream);
 }
 
 int gcsa2_seed_classes_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
@@ -6446,29 +6236,8 @@ int gcsa2_seed_classes_device(const gcsa2_index* ix, const uint64_t* d_group_off
                               uint64_t n_bins, uint64_t n_classes, uint64_t* d_votes, gcsa2_class_call* d_calls, gcsa2_class_stats* stats,
                               void* stream)
 {
-  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_group_offsets is NULL"); }
-  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_classes: d_seeds is NULL"); }
-  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more groups in one call; split the batch"); }
-  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_classes: 2^32 or more seeds in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.windows = n_seeds;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
   const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, d_votes, d_calls, 0, nullptr, nullptr};
-  {
-    Scratch scratch(ix, st);
-    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
-                      job, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_classes_device: ") + e.what()); }
+  return seed_classes_entry(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_weights, job, false, "seed_classes", stats, stream);
 }
 
 int gcsa2_kmer_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
@@ -6485,20 +6254,8 @@ int gcsa2_kmer_top_classes_device(const gcsa2_index* ix, const uint8_t* d_patter
                                   uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
                                   gcsa2_class_stats* stats, void* stream)
 {
-  int rc = kmer_classes_checks(ix, k, stride, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin", top_n, true);
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_top_classes: d_offsets is NULL"); }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_top_classes: 2^32 or more reads in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
   const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, nullptr, nullptr, top_n, d_top, d_summaries};
-  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_top_classes_device: ") + e.what()); }
+  return kmer_classes_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, job, true, "kmer_top_classes", stats, stream);
 }
 
 int gcsa2_kmer_top_classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
@@ -6514,28 +6271,8 @@ int gcsa2_seed_top_classes_device(const gcsa2_index* ix, const uint64_t* d_group
                                   uint64_t n_bins, uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
                                   gcsa2_class_stats* stats, void* stream)
 {
-  int rc = classes_checks(ix, shift, flags, d_class_of_bin, n_bins, n_classes, "d_class_of_bin", top_n, true);
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_top_classes: d_group_offsets is NULL"); }
-  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_top_classes: d_seeds is NULL"); }
-  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_top_classes: 2^32 or more groups in one call; split the batch"); }
-  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_top_classes: 2^32 or more seeds in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.windows = n_seeds;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, nullptr, nullptr, top_n, d_top, d_summaries};
-  {
-    Scratch scratch(ix, st);
-    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
-                      job, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_top_classes_device: ") + e.what()); }
+  return seed_classes_entry(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_weights, job, true, "seed_top_classes", stats, stream);
 }
 
 }  // extern "C"

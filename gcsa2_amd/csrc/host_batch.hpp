@@ -1,5 +1,6 @@
 // host_batch.hpp -- how a batch in the caller's HOST memory travels to the kernels and back: the pieces a large batch is cut
-// into, the host threads that carry them, device buffers of a call, and the chunked pipeline of the large find() batches.
+// into, the host threads that carry them, device buffers of a call, the piece loop of the read calls, and the chunked pipeline
+// of the large find() batches.
 // Host code only.  Part of the single translation unit gcsa2_hip.hip, which includes it once gcsa2_index, g_error / fail()
 // and DeviceGuard are defined; the entry points that use it keep only what is particular to their call.
 #pragma once
@@ -97,6 +98,165 @@ template<class Work> int fan_out(unsigned threads, const char* prefix, Work work
       const Outcome& o = outcome[t];
       if(o.status != GCSA2_OK && o.echo == (echoes != 0)) { return fail(o.status, prefix != nullptr ? prefix + std::to_string(t) + ": " + o.message : o.message); }
     }
+  }
+  return GCSA2_OK;
+}
+
+// ---- read batches: a host form that hands pieces of whole reads to its device form -----------------------------------------
+// Three layers.  fan_out starts the host threads.  for_read_pieces is what every host form of a read call does around its
+// device form: a batch of two pieces' worth of read bytes or more is cut into pieces of whole reads (tune.ms_piece_bytes,
+// GCSA2_MS_PIECE_MB) that tune.ms_threads host threads carry, thread t pieces t, t + threads, ..., each thread on a
+// non-blocking stream of its own when there are several pieces (the null stream if it cannot be created); a smaller batch is
+// one piece on the null stream.  seed_pieces_batch is the whole host form of the calls that return seeds with their hits.
+
+// pattern offsets handed over by a host caller: non-decreasing, or the kernels would read outside the pattern buffer
+inline bool offsets_ok(const uint64_t* offsets, uint64_t nq, u64* longest = nullptr)
+{
+  u64 bad = 0, most = 0;
+  for(u64 q = 0; q < nq; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    bad |= u64(offsets[q + 1] < offsets[q]);
+    most = (len > most ? len : most);
+  }
+  if(longest != nullptr) { *longest = most; }
+  return bad == 0;
+}
+
+// what a host form refuses of its reads (n > 0, offsets not null); with `name` the missing argument is named
+inline int reads_ok(const uint8_t* patterns, const uint64_t* offsets, u64 n, const char* name)
+{
+  if(offsets[0] != 0 || !offsets_ok(offsets, n)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "pattern offsets must start at 0 and be non-decreasing"); }
+  if(patterns == nullptr && offsets[n] > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, name != nullptr ? std::string(name) + ": patterns is NULL" : std::string("null buffer")); }
+  return GCSA2_OK;
+}
+
+// the windows of length k at every stride-th position of n reads; with `starts`, n + 1 entries: where each read's begin
+inline u64 host_windows(const uint64_t* offsets, u64 n, u64 k, u64 stride, u64* starts = nullptr)
+{
+  u64 total = 0;
+  for(u64 q = 0; q < n; q++)
+  {
+    const u64 len = offsets[q + 1] - offsets[q];
+    if(starts != nullptr) { starts[q] = total; }
+    if(len >= k) { total += (len - k) / stride + 1; }
+  }
+  if(starts != nullptr) { starts[n] = total; }
+  return total;
+}
+
+// one piece below two pieces' worth of read bytes, else cut_pieces
+inline std::vector<u64> read_cut(const gcsa2_index* ix, const uint64_t* offsets, u64 n)
+{
+  return offsets[n] < 2 * ix->tune.ms_piece_bytes ? std::vector<u64>{0, n} : cut_pieces(offsets, n, ix->tune.ms_piece_bytes);
+}
+
+// piece c of `pieces`: reads b .. b + count - 1, whose `bytes` bytes begin at patterns + first; `local`: their offsets from 0
+struct ReadPiece { u64 c, b, count, first, bytes; const u64* local; hipStream_t stream; u64 pieces; };
+
+// body(piece, outcome) -> bool for every piece of `cut` (read_cut: the caller sizes what it keeps per piece from it).  false,
+// or a failure in `outcome`, ends the thread's loop.  A form that brings its own stream (a Lease) asks for none.
+template<class Body> int for_read_pieces(const gcsa2_index* ix, const uint64_t* offsets, const std::vector<u64>& cut, Body body, bool streams = true)
+{
+  const u64 pieces = cut.size() - 1;
+  const unsigned threads = unsigned(pieces < ix->tune.ms_threads ? pieces : ix->tune.ms_threads);
+  return fan_out(threads, nullptr, [&](unsigned t, Outcome& out)
+  {
+    DeviceGuard guard(ix->device);
+    std::vector<u64> local;
+    hipStream_t stream = nullptr;
+    if(streams && pieces > 1 && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); stream = nullptr; }
+    for(u64 c = t; c < pieces && out.status == GCSA2_OK; c += threads)
+    {
+      const u64 b = cut[c], count = cut[c + 1] - b, first = offsets[b], bytes = offsets[b + count] - first;
+      rebase_piece(offsets, b, count, local);
+      if(!body(ReadPiece{c, b, count, first, bytes, local.data(), stream, pieces}, out)) { break; }
+    }
+    if(stream != nullptr) { (void)hipStreamDestroy(stream); }
+  });
+}
+
+// the piece's reads and offsets in device buffers of their own, arrived when this returns
+inline bool upload_reads(const ReadPiece& piece, const uint8_t* patterns, DBuf<u8>& d_pat, DBuf<u64>& d_off, Outcome& out)
+{
+  hipError_t e = d_pat.alloc(piece.bytes + 16);
+  if(e == hipSuccess) { e = d_off.alloc(piece.count + 1); }
+  if(e == hipSuccess && piece.bytes > 0) { e = hipMemcpyAsync(d_pat.p, patterns + piece.first, piece.bytes, hipMemcpyHostToDevice, piece.stream); }
+  if(e == hipSuccess) { e = hipMemcpyAsync(d_off.p, piece.local, (piece.count + 1) * sizeof(u64), hipMemcpyHostToDevice, piece.stream); }
+  if(e == hipSuccess) { e = hipStreamSynchronize(piece.stream); }
+  if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+  return true;
+}
+
+// The host form of a call that returns, per read, seeds (seed_offsets, seeds) and, per seed, hits (hit_offsets, hits), after
+// the caller's checks (n > 0).  The number of seeds of a piece is not known before it ran, so every piece keeps its four
+// arrays in host memory and the caller's arrays are put together from them in read order at the end, when the totals are
+// known to fit; *total_seeds and *total_hits are written whatever the outcome.  The call supplies
+//   estimate(piece) -> (rm, rh)     the seed and hit room of the piece's first run: with one piece the caller's capacities (a
+//                                   refusal is the call's), with several a guess -- a piece that the device form refuses for
+//                                   room runs once more with what the refusal asks for
+//   run(piece, d_pat, d_off, d_per_read, d_seed_off, d_seeds, rm, &m, d_hit_off, d_hits, rh, &h) -> status
+//                                   the device form on piece.stream
+// and, if the call has one, an output of per_read_bytes per read (per_read, null: none), copied to its reads' place.
+template<class Estimate, class Run>
+int seed_pieces_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n, Estimate estimate, Run run, u64 per_read_bytes,
+                      void* per_read, uint64_t* seed_offsets, gcsa2_mem* seeds, u64 seed_capacity, u64* total_seeds, uint64_t* hit_offsets,
+                      uint64_t* hits, u64 hit_capacity, u64* total_hits)
+{
+  const std::vector<u64> cut = read_cut(ix, offsets, n);
+  struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
+  std::vector<Piece> done(cut.size() - 1);
+  const int rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
+  {
+    Piece& piece = done[p.c];
+    DBuf<u8> d_pat, d_per_read; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    hipError_t e = d_seed_off.alloc(p.count + 1);
+    if(e == hipSuccess && per_read != nullptr) { e = d_per_read.alloc(p.count * per_read_bytes); }
+    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+    std::pair<u64, u64> room = estimate(p);
+    u64 &rm = room.first, &rh = room.second;
+    int piece_rc = GCSA2_OK;
+    for(int attempt = 0; attempt < 2; attempt++)
+    {
+      d_seeds.release(); d_hit_off.release(); d_hits.release();
+      e = d_seeds.alloc(rm);
+      if(e == hipSuccess) { e = d_hit_off.alloc(rm + 1); }
+      if(e == hipSuccess) { e = d_hits.alloc(rh); }
+      if(e != hipSuccess) { break; }
+      piece_rc = run(p, d_pat.p, d_off.p, d_per_read.p, d_seed_off.p, d_seeds.p, rm, &piece.m, d_hit_off.p, d_hits.p, rh, &piece.h);
+      if(piece_rc == GCSA2_ERR_BUFFER_TOO_SMALL && p.pieces > 1 && attempt == 0 && (piece.m > rm || piece.h > rh)) { rm = piece.m; rh = piece.h; continue; }
+      break;
+    }
+    if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); return false; }
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    piece.seed_off.resize(p.count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
+    e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (p.count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
+    if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && per_read != nullptr) { e = hipMemcpy(static_cast<u8*>(per_read) + p.b * per_read_bytes, d_per_read.p, p.count * per_read_bytes, hipMemcpyDeviceToHost); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    return true;
+  });
+  u64 m = 0, h = 0;
+  for(const Piece& piece : done) { m += piece.m; h += piece.h; }
+  *total_seeds = m;
+  *total_hits = h;
+  if(rc != GCSA2_OK) { return rc; }
+  if(m > seed_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed buffer too small"); }
+  if(h > hit_capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "hit buffer too small"); }
+  u64 mbase = 0, hbase = 0;
+  for(u64 c = 0; c + 1 < cut.size(); c++)
+  {
+    const Piece& piece = done[c];
+    const u64 b = cut[c], count = cut[c + 1] - b;
+    for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
+    if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
+    for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }
+    if(piece.h > 0) { std::memcpy(hits + hbase, piece.hits.data(), piece.h * sizeof(u64)); }
+    mbase += piece.m;
+    hbase += piece.h;
   }
   return GCSA2_OK;
 }
