@@ -21,6 +21,9 @@ STATUS_BUFFER_TOO_SMALL = -6
 KMER_COUNTS = 1     # GCSA2_KMER_COUNTS
 SUPPORT_PER_BIN = 1     # GCSA2_SUPPORT_PER_BIN
 SUPPORT_STATS = ("windows", "found", "counted", "distinct", "values", "added", "dropped")     # gcsa2_support_stats
+SPECTRUM_COUNTS = 1     # GCSA2_SPECTRUM_COUNTS
+SPECTRUM_STATS = ("kmers", "nodes", "occurrences", "unique", "max_value")     # gcsa2_spectrum_stats
+INDEX_KMER = ("sp", "ep", "count", "nodes", "k", "kmer0", "kmer1", "kmer2")     # gcsa2_index_kmer, the columns of list_kmers
 CLASS_NONE = 0xFFFFFFFF     # GCSA2_CLASS_NONE
 CLASS_LIMIT = 4096          # GCSA2_CLASS_LIMIT
 CLASS_PER_WINDOW = 1        # GCSA2_CLASS_PER_WINDOW
@@ -58,6 +61,7 @@ EXPORTS = [
     "gcsa2_kmer_hits_device", "gcsa2_kmer_hits_batch",
     "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
     "gcsa2_kmer_support_device", "gcsa2_kmer_support_batch", "gcsa2_seed_support_device",
+    "gcsa2_kmer_spectrum", "gcsa2_list_kmers", "gcsa2_index_kmer_support_device",
     "gcsa2_kmer_classes_device", "gcsa2_kmer_classes_batch", "gcsa2_seed_classes_device",
     "gcsa2_kmer_top_classes_device", "gcsa2_kmer_top_classes_batch", "gcsa2_seed_top_classes_device",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
@@ -186,6 +190,9 @@ def load_library():
     L.gcsa2_kmer_support_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp, vp]
     L.gcsa2_kmer_support_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp]
     L.gcsa2_seed_support_device.argtypes = [vp, vp, u64, vp, u64, u64, C.c_int, vp, u64, vp, vp]
+    L.gcsa2_kmer_spectrum.argtypes = [vp, u64, i32, i32, i32, vp, u64, vp]
+    L.gcsa2_list_kmers.argtypes = [vp, u64, i32, i32, i32, u64, u64, vp, u64, u64p]
+    L.gcsa2_index_kmer_support_device.argtypes = [vp, u64, i32, i32, u64, u64, C.c_int, vp, u64, vp, vp]
     L.gcsa2_kmer_classes_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
     L.gcsa2_kmer_classes_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp]
     L.gcsa2_seed_classes_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, C.c_int, vp, u64, u64, vp, vp, vp, vp]
@@ -711,6 +718,53 @@ class GCSA:
         if rc != 0:
             raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
         return dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
+
+    def kmer_spectrum(self, k, n_hist=4096, counts=True, include_Ns=False, force=False):
+        """The occurrence histogram of the index's own k-mers (gcsa2_kmer_spectrum): (histogram, stats).  histogram[v] is the
+        number of distinct k-mers whose value -- count(range) with counts, Range::length(range) without -- is v; the last of the
+        n_hist bins collects everything at or above it (n_hist = 0: no histogram, an empty array).  stats: a dict of
+        SPECTRUM_STATS; stats["kmers"] is count_kmers(k, include_Ns, force)."""
+        histogram = np.zeros(int(n_hist), dtype=np.uint64)
+        stats = (C.c_uint64 * len(SPECTRUM_STATS))()
+        _check(self._L.gcsa2_kmer_spectrum(self._h, int(k), int(include_Ns), int(force), SPECTRUM_COUNTS if counts else 0,
+                                           histogram.ctypes.data if histogram.shape[0] else None, histogram.shape[0], stats))
+        return histogram, dict(zip(SPECTRUM_STATS, (int(x) for x in stats)))
+
+    def list_kmers(self, k, min_value=0, max_value=0, counts=True, include_Ns=False, force=False):
+        """The index's k-mers whose value lies in [min_value, max_value] (max_value = 0: no upper end), as an (m, 8) uint64 array
+        with the columns INDEX_KMER (gcsa2_list_kmers): a sizing call, then a filling call.  Order is unspecified; the key is
+        packed as in compare_kmers_records; `count` is 0 without counts."""
+        flags = SPECTRUM_COUNTS if counts else 0
+        total = C.c_uint64(0)
+        rc = self._L.gcsa2_list_kmers(self._h, int(k), int(include_Ns), int(force), flags, int(min_value), int(max_value), None, 0, C.byref(total))
+        if rc != STATUS_BUFFER_TOO_SMALL:
+            _check(rc)
+        records = np.zeros((total.value, 8), dtype=np.uint64)
+        if total.value:
+            _check(self._L.gcsa2_list_kmers(self._h, int(k), int(include_Ns), int(force), flags, int(min_value), int(max_value),
+                                            records.ctypes.data, total.value, C.byref(total)))
+        return records[: total.value]
+
+    def index_kmer_support_device(self, k, hit_max, shift, flags, d_support, n_bins, include_Ns=False, force=False, stream=0):
+        """gcsa2_index_kmer_support_device: every k-mer of the index with hit_max == 0 or count() <= hit_max adds 1 to
+        d_support[v >> shift] for every located value v of its range (SUPPORT_PER_BIN: once per distinct bin).  d_support: a raw
+        device pointer to n_bins u64 that are added into (0 / None with n_bins == 0: a statistics run).  Complete on return.
+        Returns the stats as a dict of SUPPORT_STATS."""
+        stats = (C.c_uint64 * len(SUPPORT_STATS))()
+        rc = self._L.gcsa2_index_kmer_support_device(self._h, int(k), int(include_Ns), int(force), int(hit_max), int(shift), int(flags),
+                                                     d_support or None, int(n_bins), stats, stream)
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(SUPPORT_STATS, (int(x) for x in stats)))
+
+    def index_kmer_support(self, k, n_bins, hit_max=0, shift=11, per_bin=False, include_Ns=False, force=False):
+        """The host convenience of index_kmer_support_device: (support, stats) with a fresh array of n_bins, through a zeroed
+        device array of the index's device (torch is the plumbing)."""
+        import torch
+        d = torch.zeros(max(int(n_bins), 1), dtype=torch.int64, device=torch.device("cuda", int(self._L.gcsa2_device(self._h))))
+        stats = self.index_kmer_support_device(k, hit_max, shift, SUPPORT_PER_BIN if per_bin else 0, d.data_ptr() if n_bins else 0, n_bins,
+                                               include_Ns=include_Ns, force=force)
+        return d[: int(n_bins)].cpu().numpy().view(np.uint64), stats
 
     def kmer_classes_batch(self, patterns, offsets, k, class_of_bin, n_classes, stride=1, hit_max=0, shift=11, per_window=False,
                            unambiguous=False, votes=True, calls=True):

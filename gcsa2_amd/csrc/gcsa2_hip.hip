@@ -23,7 +23,9 @@
 //   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
 //   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
-//   kernels_lcp.hpp     k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
+//   kernels_spectrum.hpp k_spectrum_*         the search tree of countKMers with count() / Range::length per k-mer: histogram, list,
+//                                             seed records for k_support_*  src/algorithms.cpp:364-421, src/gcsa.cpp:802-809
+//   kernels_lcp.hpp    k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
 #include "sdsl_reader.hpp"
 #include "sdsl_writer.hpp"
@@ -61,6 +63,7 @@ using namespace g2;
 #include "kernels_seeds.hpp"
 #include "kernels_support.hpp"
 #include "kernels_classes.hpp"
+#include "kernels_spectrum.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -3491,6 +3494,119 @@ int kmer_run(const gcsa2_index* ix, const u64* d_frontier, u64 n, u64 depth, u64
   if(depth == k) { total += n; }
   return GCSA2_OK;
 }
+
+// The same tree for the spectrum calls (kernels_spectrum.hpp), depth-first over pieces like kmer_run, on the caller's stream.
+// The levels above the last are k_spectrum_expand, with keys in the list mode; the last is k_spectrum_leaf on the parents at
+// depth k - 1.  SPEC_HISTOGRAM: the last level needs no buffer and takes a frontier of any size.  The emitting modes cut the
+// last level too, so that the children of a piece -- at most min(kmer_piece, SPECTRUM_EMIT_PIECE) -- fit the record buffer,
+// and hand every piece's m > 0 records (and, SPEC_SEEDS, their count()s) to `sink` before the next piece overwrites them.
+constexpr u64 SPECTRUM_EMIT_PIECE = u64(1) << 24;     // records of one piece: 1 GB of gcsa2_index_kmer, 0.8 GB of gcsa2_mem and counts
+
+// GCSA2_SPECTRUM_GROUPS (a test knob, read per call): the workgroups of k_spectrum_leaf, each of which takes every
+// gridDim.x-th tile of 256 states.  The result never depends on it.
+u64 spectrum_leaf_groups(const gcsa2_index* ix)
+{
+  u64 groups = u64(ix->compute_units) * SPECTRUM_LEAF_GROUPS_PER_CU;
+  const char* env = std::getenv("GCSA2_SPECTRUM_GROUPS");
+  if(env != nullptr && *env != 0)
+  {
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(env, &end, 10);
+    if(end != env && *end == 0 && v >= 1) { groups = v; }
+  }
+  return std::min(groups, u64(1) << 31);
+}
+
+struct SpectrumRun
+{
+  const gcsa2_index* ix; hipStream_t st; u32 limit; u64 k; int mode; int counts;
+  unsigned long long* stat; unsigned long long* hist; u64 n_hist; u64 min_value, max_value;
+  std::function<int(const u64* d_recs, const u64* d_counts, u64 m)> sink;
+  KmerBufs states, keys, records, record_counts;
+};
+
+int spectrum_run(SpectrumRun& c, const u64* frontier, const u64* keys, u64 n, u64 depth)
+{
+  const bool with_keys = (c.mode == SPEC_LIST);
+  while(depth < c.k && n > 0)
+  {
+    const bool last = (depth + 1 == c.k);
+    const u64 piece = (last ? std::min<u64>(c.ix->tune.kmer_piece, SPECTRUM_EMIT_PIECE) : c.ix->tune.kmer_piece);
+    if(!(last && c.mode == SPEC_HISTOGRAM) && n * c.limit > piece && n > 1)      // halves, one after the other, in place
+    {
+      const u64 half = n / 2;
+      int rc = spectrum_run(c, frontier, keys, half, depth);
+      if(rc == GCSA2_OK) { rc = spectrum_run(c, frontier + 2 * half, (keys != nullptr ? keys + 3 * half : nullptr), n - half, depth); }
+      return rc;
+    }
+    const u64 room = n * c.limit;
+    unsigned long long produced = 0;
+    HIP_TRY(hipMemsetAsync(c.stat + SPEC_CURSOR, 0, sizeof(unsigned long long), c.st));
+    if(last)
+    {
+      u64 *recs = nullptr, *rec_counts = nullptr;
+      const dim3 leaf_grid(unsigned(std::min<u64>((n + TPB - 1) / TPB, spectrum_leaf_groups(c.ix))));
+      if(c.mode == SPEC_HISTOGRAM)
+      {
+        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_HISTOGRAM>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
+                           c.counts, c.hist, c.n_hist, c.stat, u64(0), u64(0), recs, rec_counts, u64(0));
+        LAUNCH_CHECK("k_spectrum_leaf");
+        return GCSA2_OK;
+      }
+      if(c.mode == SPEC_SEEDS)
+      {
+        HIP_TRY(c.records.get(0, size_t(room * 5 * sizeof(u64)), recs));
+        HIP_TRY(c.record_counts.get(0, size_t(room * sizeof(u64)), rec_counts));
+        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_SEEDS>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
+                           c.counts, c.hist, c.n_hist, c.stat, u64(0), u64(0), recs, rec_counts, room);
+      }
+      else
+      {
+        HIP_TRY(c.records.get(0, size_t(room * 8 * sizeof(u64)), recs));
+        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_LIST>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
+                           c.counts, c.hist, c.n_hist, c.stat, c.min_value, c.max_value, recs, rec_counts, room);
+      }
+      LAUNCH_CHECK("k_spectrum_leaf");
+      HIP_TRY(hipMemcpyAsync(&produced, c.stat + SPEC_CURSOR, sizeof(produced), hipMemcpyDeviceToHost, c.st));
+      HIP_TRY(hipStreamSynchronize(c.st));
+      if(produced > room) { return fail(GCSA2_ERR_HIP, "k-mer spectrum: more records than a piece has room for"); }
+      return (produced > 0 ? c.sink(recs, rec_counts, produced) : GCSA2_OK);
+    }
+    u64 *next = nullptr, *next_keys = nullptr;
+    HIP_TRY(c.states.get(size_t(depth + 1), size_t(room * 2 * sizeof(u64)), next));
+    if(with_keys)
+    {
+      HIP_TRY(c.keys.get(size_t(depth + 1), size_t(room * 3 * sizeof(u64)), next_keys));
+      hipLaunchKernelGGL((k_spectrum_expand<true>), dim3(grid_for(n)), dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth), next,
+                         next_keys, room, c.stat + SPEC_CURSOR);
+    }
+    else
+    {
+      hipLaunchKernelGGL((k_spectrum_expand<false>), dim3(grid_for(n)), dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth), next,
+                         next_keys, room, c.stat + SPEC_CURSOR);
+    }
+    LAUNCH_CHECK("k_spectrum_expand");
+    HIP_TRY(hipMemcpyAsync(&produced, c.stat + SPEC_CURSOR, sizeof(produced), hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    if(produced > room) { return fail(GCSA2_ERR_HIP, "k-mer spectrum: more states than a piece has room for"); }
+    frontier = next; keys = next_keys; n = produced; depth++;
+  }
+  return GCSA2_OK;
+}
+
+// The walk from the root: c.stat is SPEC_WORDS cleared words at the end of which the five sums stand (read them after the
+// stream has been waited for; spectrum_run leaves the last leaf kernel of the histogram mode in flight).
+int spectrum_walk(SpectrumRun& c)
+{
+  u64 *frontier = nullptr, *keys = nullptr;
+  HIP_TRY(c.states.get(0, 2 * sizeof(u64), frontier));
+  const u64 root[2] = {0, c.ix->img.n - 1};
+  HIP_TRY(hipMemcpyAsync(frontier, root, sizeof(root), hipMemcpyHostToDevice, c.st));
+  if(c.mode == SPEC_LIST) { HIP_TRY(c.keys.get(0, 3 * sizeof(u64), keys)); HIP_TRY(hipMemsetAsync(keys, 0, 3 * sizeof(u64), c.st)); }
+  HIP_TRY(hipMemsetAsync(c.stat, 0, SPEC_WORDS * sizeof(unsigned long long), c.st));
+  HIP_TRY(hipStreamSynchronize(c.st));          // `root` is pageable stack memory
+  return spectrum_run(c, frontier, keys, 1, 0);
+}
 }  // namespace
 
 extern "C" int gcsa2_count_kmers(const gcsa2_index* ix, uint64_t k, int include_ns, int force, uint64_t* result)
@@ -5865,6 +5981,141 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
   if(stats != nullptr) { *stats = sums; }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_support_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== index k-mer spectrum: the k-mers of the index itself, binned, listed or summed per graph node (kernels_spectrum.hpp) ====
+namespace {
+
+// what the three calls refuse before any device is touched
+int spectrum_checks(const gcsa2_index* ix, u64 k, int flags, int known_flags, const char* name)
+{
+  CHECK_INDEX(ix);
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": k must be at least 1"); }
+  if((flags & ~known_flags) != 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": unknown flags"); }
+  if(ix->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": alphabet too small for countKMers"); }
+  return GCSA2_OK;
+}
+
+int spectrum_counters(const gcsa2_index* ix, int flags, const char* name)
+{
+  if((flags & GCSA2_SPECTRUM_COUNTS) != 0 && !ix->img.has_counters)
+  {
+    return fail(GCSA2_ERR_MISSING_COMPONENT, std::string(name) + ": GCSA2_SPECTRUM_COUNTS on an index that was created without counters");
+  }
+  return GCSA2_OK;
+}
+
+// countKMers returns 0 for these (algorithms.cpp:391-395); so does every output here
+inline bool spectrum_nothing(const gcsa2_index* ix, u64 k, int force) { return (k > ix->order && !force) || ix->img.n == 0; }
+
+inline u32 spectrum_limit(const gcsa2_index* ix, int include_ns) { return u32(include_ns ? ix->img.sigma - 2 : ix->img.fast_chars); }
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_kmer_spectrum(const gcsa2_index* ix, uint64_t k, int include_ns, int force, int flags, uint64_t* histogram, uint64_t n_hist,
+                        gcsa2_spectrum_stats* stats)
+{
+  int rc = spectrum_checks(ix, k, flags, GCSA2_SPECTRUM_COUNTS, "kmer_spectrum");
+  if(rc != GCSA2_OK) { return rc; }
+  if(histogram == nullptr && n_hist > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_spectrum: histogram is NULL with n_hist > 0"); }
+  rc = spectrum_counters(ix, flags, "kmer_spectrum");
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  for(u64 i = 0; i < n_hist; i++) { histogram[i] = 0; }
+  gcsa2_spectrum_stats sums{};
+  if(stats != nullptr) { *stats = sums; }
+  if(spectrum_nothing(ix, k, force)) { return GCSA2_OK; }
+  DeviceGuard guard(ix->device);
+  DBuf<unsigned long long> stat, hist;
+  HIP_TRY(stat.alloc(SPEC_WORDS));
+  if(n_hist > 0) { HIP_TRY(hist.alloc(n_hist)); HIP_TRY(hipMemset(hist.p, 0, n_hist * sizeof(unsigned long long))); }
+  SpectrumRun run{ix, nullptr, spectrum_limit(ix, include_ns), k, SPEC_HISTOGRAM, int((flags & GCSA2_SPECTRUM_COUNTS) != 0), stat.p,
+                  (n_hist > 0 ? hist.p : nullptr), n_hist, 0, 0, nullptr};
+  rc = spectrum_walk(run);
+  if(rc != GCSA2_OK) { return rc; }
+  unsigned long long host_stat[SPEC_WORDS];
+  HIP_TRY(hipMemcpy(host_stat, stat.p, sizeof(host_stat), hipMemcpyDeviceToHost));
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histogram is copied as it stands");
+  if(n_hist > 0) { HIP_TRY(hipMemcpy(histogram, hist.p, n_hist * sizeof(u64), hipMemcpyDeviceToHost)); }
+  sums.kmers = host_stat[SPEC_KMERS]; sums.nodes = host_stat[SPEC_NODES]; sums.occurrences = host_stat[SPEC_OCCURRENCES];
+  sums.unique = host_stat[SPEC_UNIQUE]; sums.max_value = host_stat[SPEC_MAX];
+  if(stats != nullptr) { *stats = sums; }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_spectrum: ") + e.what()); }
+}
+
+int gcsa2_list_kmers(const gcsa2_index* ix, uint64_t k, int include_ns, int force, int flags, uint64_t min_value, uint64_t max_value,
+                     gcsa2_index_kmer* records, uint64_t capacity, uint64_t* total)
+{
+  int rc = spectrum_checks(ix, k, flags, GCSA2_SPECTRUM_COUNTS, "list_kmers");
+  if(rc != GCSA2_OK) { return rc; }
+  if(total == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: total is NULL"); }
+  if(k > 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: k must be at most 64 (the key holds 64 steps)"); }
+  if(max_value != 0 && min_value > max_value) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: min_value exceeds max_value"); }
+  if(records == nullptr && capacity > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: records is NULL with capacity > 0"); }
+  rc = spectrum_counters(ix, flags, "list_kmers");
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  *total = 0;
+  if(spectrum_nothing(ix, k, force)) { return GCSA2_OK; }
+  static_assert(sizeof(gcsa2_index_kmer) == 8 * sizeof(u64), "gcsa2_index_kmer is eight words");
+  DeviceGuard guard(ix->device);
+  DBuf<unsigned long long> stat;
+  HIP_TRY(stat.alloc(SPEC_WORDS));
+  u64 listed = 0;
+  SpectrumRun run{ix, nullptr, spectrum_limit(ix, include_ns), k, SPEC_LIST, int((flags & GCSA2_SPECTRUM_COUNTS) != 0), stat.p, nullptr, 0,
+                  min_value, max_value, nullptr};
+  run.sink = [&](const u64* d_recs, const u64*, u64 m) -> int     // a piece that no longer fits is counted, not copied
+  {
+    if(listed + m <= capacity) { HIP_TRY(hipMemcpy(records + listed, d_recs, m * sizeof(gcsa2_index_kmer), hipMemcpyDeviceToHost)); }
+    listed += m;
+    return GCSA2_OK;
+  };
+  rc = spectrum_walk(run);
+  if(rc != GCSA2_OK) { return rc; }
+  *total = listed;
+  if(listed > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "list_kmers: capacity is smaller than *total"); }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_list_kmers: ") + e.what()); }
+}
+
+int gcsa2_index_kmer_support_device(const gcsa2_index* ix, uint64_t k, int include_ns, int force, uint64_t hit_max, uint64_t shift, int flags,
+                                    uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream)
+{
+  CHECK_INDEX(ix);
+  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "index_kmer_support: k must be at least 1"); }
+  if(ix->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "index_kmer_support: alphabet too small for countKMers"); }
+  int rc = support_checks(ix, shift, flags, d_support, n_bins, "d_support");
+  if(rc != GCSA2_OK) { return rc; }
+  gcsa2_support_stats sums{};
+  if(spectrum_nothing(ix, k, force)) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  DeviceGuard guard(ix->device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  DBuf<unsigned long long> stat;
+  HIP_TRY(stat.alloc(SPEC_WORDS));
+  SpectrumRun run{ix, st, spectrum_limit(ix, include_ns), k, SPEC_SEEDS, 1, stat.p, nullptr, 0, 0, 0, nullptr};
+  run.sink = [&](const u64* d_recs, const u64* d_counts, u64 m) -> int       // one piece: the core of gcsa2_seed_support_device
+  {
+    gcsa2_support_stats piece{};
+    Scratch scratch(ix, st);
+    const int piece_rc = support_tail(ix, d_recs, 5, d_counts, nullptr, m, hit_max, shift, flags, d_support, n_bins, &piece, scratch, st);
+    if(piece_rc != GCSA2_OK) { return piece_rc; }
+    sums.windows += m; sums.found += piece.found; sums.counted += piece.counted; sums.distinct += piece.distinct;
+    sums.values += piece.values; sums.added += piece.added; sums.dropped += piece.dropped;
+    return GCSA2_OK;
+  };
+  rc = spectrum_walk(run);
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_index_kmer_support_device: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -213,6 +213,34 @@ inline size_type countKMers(const GCSA& index, size_type k, const KMerSearchPara
   return result;
 }
 
+// The occurrence spectrum of the k-mers countKMers counts (gcsa2_kmer_spectrum): histogram[min(value, size() - 1)] is the
+// number of k-mers with that value -- count(range) with `counts`, Range::length(range) without -- for the size the caller
+// gives the vector (it is overwritten; an empty one asks for the statistics alone).  Returns {kmers, nodes, occurrences,
+// unique, max_value}; kmers == countKMers(index, k, parameters).
+inline gcsa2_spectrum_stats kmerSpectrum(const GCSA& index, size_type k, const KMerSearchParameters& parameters,
+                                         std::vector<size_type>& histogram, bool counts = true)
+{
+  gcsa2_spectrum_stats stats = {0, 0, 0, 0, 0};
+  check(gcsa2_kmer_spectrum(index.handle, k, parameters.include_Ns ? 1 : 0, parameters.force ? 1 : 0, counts ? GCSA2_SPECTRUM_COUNTS : 0,
+                            histogram.empty() ? nullptr : histogram.data(), histogram.size(), &stats), "kmerSpectrum()");
+  return stats;
+}
+
+// The k-mers themselves (gcsa2_list_kmers): those with min_value <= value and (max_value == 0 or value <= max_value), as
+// {sp, ep, count, nodes, k, kmer[3]} with the key packing of compareKMers' dumps, in no specified order.  k <= 64.
+inline std::vector<gcsa2_index_kmer> listKMers(const GCSA& index, size_type k, const KMerSearchParameters& parameters = KMerSearchParameters(),
+                                               size_type min_value = 0, size_type max_value = 0, bool counts = true)
+{
+  const int ns = parameters.include_Ns ? 1 : 0, force = parameters.force ? 1 : 0, flags = counts ? GCSA2_SPECTRUM_COUNTS : 0;
+  uint64_t total = 0;
+  const int rc = gcsa2_list_kmers(index.handle, k, ns, force, flags, min_value, max_value, nullptr, 0, &total);
+  if(rc != GCSA2_ERR_BUFFER_TOO_SMALL) { check(rc, "listKMers()"); }
+  std::vector<gcsa2_index_kmer> records(total);
+  if(total > 0) { check(gcsa2_list_kmers(index.handle, k, ns, force, flags, min_value, max_value, records.data(), records.size(), &total), "listKMers()"); }
+  records.resize(total);
+  return records;
+}
+
 // compareKMers(left, right, k, parameters) (include/gcsa/algorithms.h:86-92): {shared, left only, right only}.
 // With parameters.output set, the states of the unique k-mers go to output + ".left" / ".right" as in the
 // reference (src/algorithms.cpp:562-610; 64 bytes per state, unordered).

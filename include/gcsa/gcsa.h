@@ -373,6 +373,17 @@ public:
     check(rc, "GCSA::kmer_support_batch()");
   }
 
+  // The denominator of kmer_support_batch (gcsa2_index_kmer_support_device): every k-mer of the INDEX with hit_max == 0 or
+  // count(range) <= hit_max adds 1 to d_support[v >> shift] for every located value v of its range (per_bin: once per distinct
+  // bin).  d_support is DEVICE memory of n_bins words that is added into (nullptr with n_bins == 0: the statistics alone).
+  void index_kmer_support_device(size_type k, bool include_Ns, bool force, size_type hit_max, size_type shift, bool per_bin,
+                                 size_type* d_support, size_type n_bins, gcsa2_support_stats* stats = nullptr, void* stream = nullptr) const
+  {
+    const int rc = gcsa2_index_kmer_support_device(handle, k, include_Ns ? 1 : 0, force ? 1 : 0, hit_max, shift, per_bin ? GCSA2_SUPPORT_PER_BIN : 0,
+                                                   d_support, n_bins, stats, stream);
+    check(rc, "GCSA::index_kmer_support_device()");
+  }
+
   // A read classifier's or binner's lookup in one call (gcsa2_kmer_classes_batch): every window P_q[j stride, j stride + k) with
   // a non-empty find() and hit_max == 0 or count(range) <= hit_max votes, in the row of its read, for the class
   // class_of_bin[v >> shift] of every located value v of its range (GCSA2_CLASS_NONE, an id >= n_classes or a bin beyond the

@@ -858,6 +858,63 @@ int gcsa2_kmer_support_batch(const gcsa2_index* index, const uint8_t* patterns, 
 int gcsa2_seed_support_device(const gcsa2_index* index, const gcsa2_mem* d_seeds, uint64_t n_seeds,
                               const uint64_t* d_weights /* or NULL = 1 each */, uint64_t hit_max, uint64_t shift, int flags,
                               uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream);
+/* ---- index k-mer spectrum: the k-mers of the INDEX, binned by occurrence, listed, or summed per graph node -------------------
+ * Every read-side call above takes a threshold that is a property of the index, not of the reads: hit_max of the MEM, k-mer
+ * and capped-seed hits, max_count of the capped seeds, the hit_max cap of k-mer support, classes and top classes.  These three
+ * calls are what a caller chooses them by.  They share one walk of the search tree of countKMers (src/algorithms.cpp:364-421).
+ *
+ * DEFINITION.
+ *   - K(k, include_ns) is the multiset of states at depth k of that tree: the root is (0, size() - 1); the children of a state
+ *     are LF_fast(range) (comps 1 .. fast_chars) when include_ns == 0, LF_all(range) (comps 1 .. sigma - 2) otherwise; only
+ *     non-empty children survive.  There is one state per distinct k-mer.  Distinct k-mers need NOT have distinct ranges: a
+ *     path node whose label is shorter than k starts several k-mers, and all of them end in its range.
+ *   - Every state carries its key in the packing of gcsa2_compare_kmers_records: the comp of extension step i at bits
+ *     [3i, 3i + 3) of kmer[3], step 0 being the LAST character of the k-mer.
+ *   - value(state) = GCSA::count(range) with GCSA2_SPECTRUM_COUNTS, Range::length(range) without it; count() is then never
+ *     evaluated, and the call works on an image without counters.
+ *
+ * gcsa2_kmer_spectrum: histogram (host, n_hist words, or NULL with n_hist == 0) is OVERWRITTEN: histogram[min(value, n_hist - 1)]
+ * is the number of states of K with that value, so the last bin collects everything at or above it and the bins sum to
+ * stats.kmers.  stats (host, may be NULL): kmers = |K| = gcsa2_count_kmers for the same (k, include_ns, force); nodes = the sum
+ * of Range::length; occurrences = the sum of count(), 0 without GCSA2_SPECTRUM_COUNTS (as in the k-mer windows profile);
+ * unique = the states of value 1; max_value = the largest value.
+ *
+ * gcsa2_list_kmers: records (host) receives the states with min_value <= value and (max_value == 0 or value <= max_value), in
+ * no specified order; `count` is 0 without GCSA2_SPECTRUM_COUNTS, `nodes` is Range::length.  *total is always the number
+ * needed.  If it exceeds capacity the call fails with GCSA2_ERR_BUFFER_TOO_SMALL; nothing is ever written behind capacity, and
+ * what lies before it is unspecified.  records == NULL with capacity == 0 is a sizing call.
+ *
+ * gcsa2_index_kmer_support_device: by composition, the records {position 0, length k, sp, ep} of K, weight 1 each, piece of
+ * the walk by piece, through the core of gcsa2_seed_support_device.  It ADDS and never zeroes.  d_support, windows, found,
+ * counted, added and dropped are exact, and windows == found == the stats.kmers of gcsa2_kmer_spectrum; distinct and values are
+ * per-piece sums -- equal ranges fold within a piece only -- exact when the walk is one piece and upper bounds otherwise, the
+ * rule of gcsa2_kmer_support_batch (which states share a piece depends on the arrival order of the levels above, so these two
+ * figures may differ from run to run when there are several pieces).  d_support[node] over the k-mers with count() <= hit_max is the denominator of
+ * gcsa2_kmer_support_device's per-node sums: the k-mers a node can be seen by under the same cap.  Needs the samples and the
+ * counters.  Enqueued on `stream`, complete on return; not transactional, as gcsa2_kmer_support_device.
+ *
+ * All three: k > order() without force, or an index of size 0, is GCSA2_OK with every output zero, as countKMers.
+ * GCSA2_ERR_INVALID_ARGUMENT, with nothing written and before any device is touched: a NULL index, k == 0, an unknown flag,
+ * sigma < 3, histogram == NULL with n_hist > 0, min_value > max_value != 0, k > 64 for the list (the key holds 64 steps),
+ * records == NULL with capacity > 0, shift >= 64, d_support == NULL with n_bins > 0, a NULL total.  GCSA2_ERR_MISSING_COMPONENT,
+ * likewise: GCSA2_SPECTRUM_COUNTS on an image without counters; support on an image without samples or counters.
+ *
+ * The walk is depth-first over pieces of the frontier (GCSA2_KMER_PIECE, as gcsa2_count_kmers): no result but distinct and
+ * values depends on the cut.  The histogram call never stores the last level; the other two cut it so that a piece holds at
+ * most 2^24 records.  GCSA2_SPECTRUM_GROUPS (workgroups of the last level's kernel, read per call; default 12 per compute unit)
+ * is a test knob: no result depends on it.  profiles/kmer_spectrum.md. */
+#define GCSA2_SPECTRUM_COUNTS 1   /* value = count(range), not Range::length(range) */
+typedef struct gcsa2_spectrum_stats { uint64_t kmers, nodes, occurrences, unique, max_value; } gcsa2_spectrum_stats;
+typedef struct gcsa2_index_kmer { uint64_t sp, ep, count, nodes, k, kmer[3]; } gcsa2_index_kmer;   /* 64 bytes */
+int gcsa2_kmer_spectrum(const gcsa2_index* index, uint64_t k, int include_ns, int force, int flags,
+                        uint64_t* histogram /* host, n_hist, or NULL */, uint64_t n_hist,
+                        gcsa2_spectrum_stats* stats /* host, or NULL */);
+int gcsa2_list_kmers(const gcsa2_index* index, uint64_t k, int include_ns, int force, int flags,
+                     uint64_t min_value, uint64_t max_value /* 0 = none */,
+                     gcsa2_index_kmer* records /* host */, uint64_t capacity, uint64_t* total);
+int gcsa2_index_kmer_support_device(const gcsa2_index* index, uint64_t k, int include_ns, int force,
+                                    uint64_t hit_max, uint64_t shift, int flags /* GCSA2_SUPPORT_PER_BIN */,
+                                    uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream);
 /* ---- k-mer classes: per read, the votes of its k-mers (or any seed records) over classes of graph nodes -----------------------
  * The transpose of k-mer support, for a read classifier or binner: per READ, on which class of graph nodes -- chromosome,
  * contig, subgraph, host or contaminant -- do its k-mers land?  With gcsa2_kmer_hits_batch the caller would pull every hit of
