@@ -3,7 +3,7 @@
 //
 // One translation unit: the device code lives in kernels_*.hpp, this file holds the host side
 // (device image staging, handles, launches, the extern "C" entry points); what carries a batch in host memory to the
-// kernels and back is in host_batch.hpp.
+// kernels and back is in host_batch.hpp, the index-side k-mer calls in host_kmers.hpp.
 //
 // Kernel <-> reference map (paths relative to the reference tree):
 //   kernels_find.hpp    k_find2 / k_find      GCSA::find                 include/gcsa/gcsa.h:96-110
@@ -13,7 +13,6 @@
 //   kernels_locate.hpp  k_count               GCSA::count, Sada*::count  src/gcsa.cpp:802-809, support.h:255-258,329-335
 //                       k_locate_*            GCSA::locate(range), locateInternal, removeDuplicates
 //                                                                        src/gcsa.cpp:827-842, 880-896, utils.h:350-357
-//                       k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
 //   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
 //                       k_kmer_seeds          the same search, emitting the found windows as seed records (gcsa2_kmer_hits_device)
@@ -23,7 +22,9 @@
 //   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
 //   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
-//   kernels_spectrum.hpp k_spectrum_*         the search tree of countKMers with count() / Range::length per k-mer: histogram, list,
+//   kernels_kmers.hpp   k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
+//                       k_kmer_compare        compareKMers               src/algorithms.cpp:505-616
+//                       k_spectrum_leaf       the last level of the same tree with count() / Range::length per k-mer: histogram, list,
 //                                             seed records for k_support_*  src/algorithms.cpp:364-421, src/gcsa.cpp:802-809
 //   kernels_lcp.hpp    k_parent / k_depth / k_sv / k_rmq   LCPArray     include/gcsa/lcp.h:137-178, src/lcp.cpp:276-519
 #include "layout.hpp"
@@ -63,7 +64,7 @@ using namespace g2;
 #include "kernels_seeds.hpp"
 #include "kernels_support.hpp"
 #include "kernels_classes.hpp"
-#include "kernels_spectrum.hpp"
+#include "kernels_kmers.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
 
@@ -3422,218 +3423,6 @@ int gcsa2_group_find_batch(const gcsa2_group* g, const uint8_t* patterns, const 
 
 }  // extern "C"
 
-// countKMers(index, k, parameters) (src/algorithms.cpp:387-421): level-synchronous frontier
-// expansion on the device instead of the reference's seed DFS + OpenMP; the count is the number of
-// non-empty states at depth k either way.
-namespace {
-int kmer_level(const gcsa2_index* ix, const u64* d_in, u64 n_in, u32 limit, u64* d_out, unsigned long long* d_counter, u64& produced)
-{
-  HIP_TRY(hipMemset(d_counter, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(k_kmer_expand, dim3(grid_for(n_in)), dim3(TPB), 0, nullptr, ix->img, d_in, n_in, limit, d_out, d_counter);
-  LAUNCH_CHECK("k_kmer_expand");
-  unsigned long long c = 0;
-  HIP_TRY(hipMemcpy(&c, d_counter, sizeof(c), hipMemcpyDeviceToHost));
-  produced = c;
-  return GCSA2_OK;
-}
-
-// One frontier buffer per depth of the search, reused by every piece of that depth (a depth-first walk over pieces: when a
-// piece of depth d is taken up, everything below the piece before it is finished) and grown to the largest piece seen.
-struct KmerBufs
-{
-  std::vector<u64*> p; std::vector<size_t> cap;
-  ~KmerBufs() { for(u64* q : p) { if(q != nullptr) { (void)hipFree(q); } } }
-  hipError_t get(size_t depth, size_t bytes, u64*& out)
-  {
-    if(p.size() <= depth) { p.resize(depth + 1, nullptr); cap.resize(depth + 1, 0); }
-    if(cap[depth] < bytes)
-    {
-      if(p[depth] != nullptr) { (void)hipFree(p[depth]); p[depth] = nullptr; cap[depth] = 0; }
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&p[depth]), bytes);
-      if(e != hipSuccess) { p[depth] = nullptr; return e; }
-      cap[depth] = bytes;
-    }
-    out = p[depth];
-    return hipSuccess;
-  }
-};
-
-// The level-synchronous search tree of countKMers below a frontier of `n` states (pairs sp, ep) at depth `depth`.  A frontier
-// whose children might not fit one 2 GB buffer (n x limit > 2^27) is cut in halves that are searched one after the other IN
-// PLACE; the children of a piece go into the buffer of their depth.  (Until late round 4 the halves were copied, larger levels
-// were expanded twice -- a counting pass, then a filling pass -- and every piece allocated and freed its buffer: k = 17 on the
-// 5.73 G-node index, a last frontier of 3.4 G states, took 4.5 s, most of it in hipMalloc / hipFree of gigabyte blocks.)
-int kmer_run(const gcsa2_index* ix, const u64* d_frontier, u64 n, u64 depth, u64 k, u32 limit, unsigned long long* d_counter, u64& total, KmerBufs& bufs)
-{
-  const u64 MAX_CHILDREN = ix->tune.kmer_piece;   // 2^27 states = 2 GB (GCSA2_KMER_PIECE: tests cut finer)
-  while(depth < k && n > 0)
-  {
-    u64 produced = 0;
-    int rc = GCSA2_OK;
-    if(depth + 1 == k)      // last level: the children only have to be counted (no buffer: any size)
-    {
-      rc = kmer_level(ix, d_frontier, n, limit, nullptr, d_counter, produced);
-      if(rc != GCSA2_OK) { return rc; }
-      total += produced;
-      return GCSA2_OK;
-    }
-    if(n * limit > MAX_CHILDREN && n > 1)
-    {
-      const u64 half = n / 2;
-      rc = kmer_run(ix, d_frontier, half, depth, k, limit, d_counter, total, bufs);
-      if(rc == GCSA2_OK) { rc = kmer_run(ix, d_frontier + 2 * half, n - half, depth, k, limit, d_counter, total, bufs); }
-      return rc;
-    }
-    u64* next = nullptr;           // one pass into the buffer of the next depth, sized for the worst case (`limit` children per state)
-    HIP_TRY(bufs.get(size_t(depth + 1), size_t(n * limit * 2 * sizeof(u64)), next));
-    rc = kmer_level(ix, d_frontier, n, limit, next, d_counter, produced);
-    if(rc != GCSA2_OK) { return rc; }
-    if(produced == 0) { return GCSA2_OK; }
-    d_frontier = next; n = produced; depth++;
-  }
-  if(depth == k) { total += n; }
-  return GCSA2_OK;
-}
-
-// The same tree for the spectrum calls (kernels_spectrum.hpp), depth-first over pieces like kmer_run, on the caller's stream.
-// The levels above the last are k_spectrum_expand, with keys in the list mode; the last is k_spectrum_leaf on the parents at
-// depth k - 1.  SPEC_HISTOGRAM: the last level needs no buffer and takes a frontier of any size.  The emitting modes cut the
-// last level too, so that the children of a piece -- at most min(kmer_piece, SPECTRUM_EMIT_PIECE) -- fit the record buffer,
-// and hand every piece's m > 0 records (and, SPEC_SEEDS, their count()s) to `sink` before the next piece overwrites them.
-constexpr u64 SPECTRUM_EMIT_PIECE = u64(1) << 24;     // records of one piece: 1 GB of gcsa2_index_kmer, 0.8 GB of gcsa2_mem and counts
-
-// GCSA2_SPECTRUM_GROUPS (a test knob, read per call): the workgroups of k_spectrum_leaf, each of which takes every
-// gridDim.x-th tile of 256 states.  The result never depends on it.
-u64 spectrum_leaf_groups(const gcsa2_index* ix)
-{
-  u64 groups = u64(ix->compute_units) * SPECTRUM_LEAF_GROUPS_PER_CU;
-  const char* env = std::getenv("GCSA2_SPECTRUM_GROUPS");
-  if(env != nullptr && *env != 0)
-  {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(env, &end, 10);
-    if(end != env && *end == 0 && v >= 1) { groups = v; }
-  }
-  return std::min(groups, u64(1) << 31);
-}
-
-struct SpectrumRun
-{
-  const gcsa2_index* ix; hipStream_t st; u32 limit; u64 k; int mode; int counts;
-  unsigned long long* stat; unsigned long long* hist; u64 n_hist; u64 min_value, max_value;
-  std::function<int(const u64* d_recs, const u64* d_counts, u64 m)> sink;
-  KmerBufs states, keys, records, record_counts;
-};
-
-int spectrum_run(SpectrumRun& c, const u64* frontier, const u64* keys, u64 n, u64 depth)
-{
-  const bool with_keys = (c.mode == SPEC_LIST);
-  while(depth < c.k && n > 0)
-  {
-    const bool last = (depth + 1 == c.k);
-    const u64 piece = (last ? std::min<u64>(c.ix->tune.kmer_piece, SPECTRUM_EMIT_PIECE) : c.ix->tune.kmer_piece);
-    if(!(last && c.mode == SPEC_HISTOGRAM) && n * c.limit > piece && n > 1)      // halves, one after the other, in place
-    {
-      const u64 half = n / 2;
-      int rc = spectrum_run(c, frontier, keys, half, depth);
-      if(rc == GCSA2_OK) { rc = spectrum_run(c, frontier + 2 * half, (keys != nullptr ? keys + 3 * half : nullptr), n - half, depth); }
-      return rc;
-    }
-    const u64 room = n * c.limit;
-    unsigned long long produced = 0;
-    HIP_TRY(hipMemsetAsync(c.stat + SPEC_CURSOR, 0, sizeof(unsigned long long), c.st));
-    if(last)
-    {
-      u64 *recs = nullptr, *rec_counts = nullptr;
-      const dim3 leaf_grid(unsigned(std::min<u64>((n + TPB - 1) / TPB, spectrum_leaf_groups(c.ix))));
-      if(c.mode == SPEC_HISTOGRAM)
-      {
-        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_HISTOGRAM>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
-                           c.counts, c.hist, c.n_hist, c.stat, u64(0), u64(0), recs, rec_counts, u64(0));
-        LAUNCH_CHECK("k_spectrum_leaf");
-        return GCSA2_OK;
-      }
-      if(c.mode == SPEC_SEEDS)
-      {
-        HIP_TRY(c.records.get(0, size_t(room * 5 * sizeof(u64)), recs));
-        HIP_TRY(c.record_counts.get(0, size_t(room * sizeof(u64)), rec_counts));
-        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_SEEDS>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
-                           c.counts, c.hist, c.n_hist, c.stat, u64(0), u64(0), recs, rec_counts, room);
-      }
-      else
-      {
-        HIP_TRY(c.records.get(0, size_t(room * 8 * sizeof(u64)), recs));
-        hipLaunchKernelGGL((k_spectrum_leaf<SPEC_LIST>), leaf_grid, dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth),
-                           c.counts, c.hist, c.n_hist, c.stat, c.min_value, c.max_value, recs, rec_counts, room);
-      }
-      LAUNCH_CHECK("k_spectrum_leaf");
-      HIP_TRY(hipMemcpyAsync(&produced, c.stat + SPEC_CURSOR, sizeof(produced), hipMemcpyDeviceToHost, c.st));
-      HIP_TRY(hipStreamSynchronize(c.st));
-      if(produced > room) { return fail(GCSA2_ERR_HIP, "k-mer spectrum: more records than a piece has room for"); }
-      return (produced > 0 ? c.sink(recs, rec_counts, produced) : GCSA2_OK);
-    }
-    u64 *next = nullptr, *next_keys = nullptr;
-    HIP_TRY(c.states.get(size_t(depth + 1), size_t(room * 2 * sizeof(u64)), next));
-    if(with_keys)
-    {
-      HIP_TRY(c.keys.get(size_t(depth + 1), size_t(room * 3 * sizeof(u64)), next_keys));
-      hipLaunchKernelGGL((k_spectrum_expand<true>), dim3(grid_for(n)), dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth), next,
-                         next_keys, room, c.stat + SPEC_CURSOR);
-    }
-    else
-    {
-      hipLaunchKernelGGL((k_spectrum_expand<false>), dim3(grid_for(n)), dim3(TPB), 0, c.st, c.ix->img, frontier, keys, n, c.limit, u32(depth), next,
-                         next_keys, room, c.stat + SPEC_CURSOR);
-    }
-    LAUNCH_CHECK("k_spectrum_expand");
-    HIP_TRY(hipMemcpyAsync(&produced, c.stat + SPEC_CURSOR, sizeof(produced), hipMemcpyDeviceToHost, c.st));
-    HIP_TRY(hipStreamSynchronize(c.st));
-    if(produced > room) { return fail(GCSA2_ERR_HIP, "k-mer spectrum: more states than a piece has room for"); }
-    frontier = next; keys = next_keys; n = produced; depth++;
-  }
-  return GCSA2_OK;
-}
-
-// The walk from the root: c.stat is SPEC_WORDS cleared words at the end of which the five sums stand (read them after the
-// stream has been waited for; spectrum_run leaves the last leaf kernel of the histogram mode in flight).
-int spectrum_walk(SpectrumRun& c)
-{
-  u64 *frontier = nullptr, *keys = nullptr;
-  HIP_TRY(c.states.get(0, 2 * sizeof(u64), frontier));
-  const u64 root[2] = {0, c.ix->img.n - 1};
-  HIP_TRY(hipMemcpyAsync(frontier, root, sizeof(root), hipMemcpyHostToDevice, c.st));
-  if(c.mode == SPEC_LIST) { HIP_TRY(c.keys.get(0, 3 * sizeof(u64), keys)); HIP_TRY(hipMemsetAsync(keys, 0, 3 * sizeof(u64), c.st)); }
-  HIP_TRY(hipMemsetAsync(c.stat, 0, SPEC_WORDS * sizeof(unsigned long long), c.st));
-  HIP_TRY(hipStreamSynchronize(c.st));          // `root` is pageable stack memory
-  return spectrum_run(c, frontier, keys, 1, 0);
-}
-}  // namespace
-
-extern "C" int gcsa2_count_kmers(const gcsa2_index* ix, uint64_t k, int include_ns, int force, uint64_t* result)
-{
-  CHECK_INDEX(ix);
-  if(result == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null result"); }
-  *result = 0;
-  if(k == 0) { *result = 1; return GCSA2_OK; }                       // algorithms.cpp:390
-  if(k > ix->order && !force) { return GCSA2_OK; }                   // algorithms.cpp:391-395 (returns 0)
-  if(ix->img.n == 0) { return GCSA2_OK; }
-  if(ix->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "alphabet too small for countKMers"); }
-  u32 limit = u32(include_ns ? ix->img.sigma - 2 : ix->img.fast_chars);   // comps 1..limit (algorithms.cpp:369, 379)
-  DeviceGuard guard(ix->device);
-  DBuf<unsigned long long> counter;
-  HIP_TRY(counter.alloc(1));
-  KmerBufs bufs;
-  u64* frontier = nullptr;
-  HIP_TRY(bufs.get(0, 2 * sizeof(u64), frontier));
-  u64 root[2] = {0, ix->img.n - 1};
-  HIP_TRY(hipMemcpy(frontier, root, sizeof(root), hipMemcpyHostToDevice));
-  u64 total = 0;
-  int rc = kmer_run(ix, frontier, 1, 0, k, limit, counter.p, total, bufs);
-  if(rc != GCSA2_OK) { return rc; }
-  *result = total;
-  return GCSA2_OK;
-}
-
 // Matching statistics (LF + parent fused); see k_match_stats2.  variant 2 = one lane per pattern, 5 = persistent lanes that draw
 // patterns from a counter, 0 = the library chooses by batch size.  total_bytes = offsets[nq] when the caller knows it (GCSA2_UNKNOWN: read back from the
 // device, which waits for the stream once).
@@ -4271,115 +4060,6 @@ extern "C" int gcsa2_index_create_from_file(const char* path, int device, gcsa2_
   rc = gcsa2_index_create(&st->view, device, out);
   gcsa2_host_view_free(st);
   return rc;
-}
-
-// compareKMers(left, right, k, parameters) (src/algorithms.cpp:534-616).  With record buffers the states of
-// the unique k-mers are returned as the reference dumps them to output.left / output.right (:606-610).
-namespace {
-
-// The search below one piece of the frontier (pairs of ranges, 4 u64 per state; with records also the 3-u64 keys), depth-first
-// over pieces like countKMers (kmer_run): a frontier of any size, where round 3 refused more than 2^27 / limit states.
-struct CompareRun
-{
-  const DevImage* images; unsigned long long* counters; u32 limit; u64 k; bool records; u64 piece;
-  uint64_t* left_records; uint64_t left_capacity; uint64_t* right_records; uint64_t right_capacity;
-  u64 shared = 0, left_only = 0, right_only = 0;       // totals (the unique ones count on even when their records no longer fit)
-  KmerBufs states, keys;
-};
-
-int compare_run(CompareRun& c, const u64* frontier, const u64* keys, u64 n, u64 depth)
-{
-  unsigned long long host_counters[4] = {0, 0, 0, 0};
-  while(depth < c.k && n > 0)
-  {
-    HIP_TRY(hipMemset(c.counters, 0, 4 * sizeof(unsigned long long)));
-    if(depth + 1 == c.k)        // last level: classify the children; any size
-    {
-      hipLaunchKernelGGL(k_kmer_compare, dim3(grid_for(n)), dim3(TPB), 0, nullptr, c.images, c.images + 1, frontier, keys, n, c.limit,
-                         u32(depth), 1, (u64*)nullptr, (u64*)nullptr, c.counters, (u64*)nullptr, (u64*)nullptr);
-      LAUNCH_CHECK("k_kmer_compare");
-      HIP_TRY(hipMemcpy(host_counters, c.counters, sizeof(host_counters), hipMemcpyDeviceToHost));
-      const u64 l = host_counters[2], r = host_counters[3];
-      if(c.records && (l > 0 || r > 0) && c.left_only + l <= c.left_capacity && c.right_only + r <= c.right_capacity)
-      {
-        DBuf<u64> d_left, d_right;
-        HIP_TRY(d_left.alloc(8 * l)); HIP_TRY(d_right.alloc(8 * r));
-        HIP_TRY(hipMemset(c.counters, 0, 4 * sizeof(unsigned long long)));
-        hipLaunchKernelGGL(k_kmer_compare, dim3(grid_for(n)), dim3(TPB), 0, nullptr, c.images, c.images + 1, frontier, keys, n, c.limit,
-                           u32(depth), 2, (u64*)nullptr, (u64*)nullptr, c.counters, d_left.p, d_right.p);
-        LAUNCH_CHECK("k_kmer_compare");
-        if(l > 0) { HIP_TRY(hipMemcpy(c.left_records + 8 * c.left_only, d_left.p, 8 * l * sizeof(u64), hipMemcpyDeviceToHost)); }
-        if(r > 0) { HIP_TRY(hipMemcpy(c.right_records + 8 * c.right_only, d_right.p, 8 * r * sizeof(u64), hipMemcpyDeviceToHost)); }
-      }
-      c.shared += host_counters[1]; c.left_only += l; c.right_only += r;
-      return GCSA2_OK;
-    }
-    if(n * c.limit > c.piece && n > 1)        // the children might not fit one buffer: halves, one after the other, in place
-    {
-      const u64 half = n / 2;
-      int rc = compare_run(c, frontier, keys, half, depth);
-      if(rc == GCSA2_OK) { rc = compare_run(c, frontier + 4 * half, (keys != nullptr ? keys + 3 * half : nullptr), n - half, depth); }
-      return rc;
-    }
-    u64 *next = nullptr, *next_keys = nullptr;
-    HIP_TRY(c.states.get(size_t(depth + 1), size_t(n * c.limit * 4 * sizeof(u64)), next));
-    if(c.records) { HIP_TRY(c.keys.get(size_t(depth + 1), size_t(n * c.limit * 3 * sizeof(u64)), next_keys)); }
-    hipLaunchKernelGGL(k_kmer_compare, dim3(grid_for(n)), dim3(TPB), 0, nullptr, c.images, c.images + 1, frontier, keys, n, c.limit,
-                       u32(depth), 0, next, next_keys, c.counters, (u64*)nullptr, (u64*)nullptr);
-    LAUNCH_CHECK("k_kmer_compare");
-    HIP_TRY(hipMemcpy(host_counters, c.counters, sizeof(host_counters), hipMemcpyDeviceToHost));
-    frontier = next; keys = next_keys; n = host_counters[0]; depth++;
-  }
-  return GCSA2_OK;
-}
-
-int compare_kmers_impl(const gcsa2_index* left, const gcsa2_index* right, uint64_t k, int include_ns, int force, uint64_t* result,
-                       uint64_t* left_records, uint64_t left_capacity, uint64_t* right_records, uint64_t right_capacity, bool records)
-{
-  CHECK_INDEX(left); CHECK_INDEX(right);
-  if(result == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null result"); }
-  result[0] = result[1] = result[2] = 0;
-  if(k == 0) { result[0] = 1; return GCSA2_OK; }                                            // :539
-  if((k > left->order || k > right->order) && !force) { return GCSA2_OK; }                   // :540-549
-  if(k > 64) { return GCSA2_OK; }                                                            // :550-554 (MAX_K)
-  if(left->img.sigma != right->img.sigma || left->img.fast_chars != right->img.fast_chars) { return GCSA2_OK; }   // :556-560
-  if(left->device != right->device) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "both indexes must live on the same device"); }
-  if(left->img.n == 0 || right->img.n == 0 || left->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "empty index or alphabet too small"); }
-  try {
-  DeviceGuard guard(left->device);
-  DBuf<DevImage> images; DBuf<unsigned long long> counters;
-  HIP_TRY(images.alloc(2)); HIP_TRY(counters.alloc(4));
-  HIP_TRY(hipMemcpy(images.p, &left->img, sizeof(DevImage), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(images.p + 1, &right->img, sizeof(DevImage), hipMemcpyHostToDevice));
-  CompareRun run{images.p, counters.p, u32(include_ns ? left->img.sigma - 2 : left->img.fast_chars), k, records, left->tune.kmer_piece,
-                 left_records, left_capacity, right_records, right_capacity};
-  u64 *frontier = nullptr, *keys = nullptr;
-  HIP_TRY(run.states.get(0, 4 * sizeof(u64), frontier));
-  const u64 root[4] = {0, left->img.n - 1, 0, right->img.n - 1};
-  HIP_TRY(hipMemcpy(frontier, root, sizeof(root), hipMemcpyHostToDevice));
-  if(records) { HIP_TRY(run.keys.get(0, 3 * sizeof(u64), keys)); HIP_TRY(hipMemset(keys, 0, 3 * sizeof(u64))); }
-  const int rc = compare_run(run, frontier, keys, 1, 0);
-  if(rc != GCSA2_OK) { return rc; }
-  result[0] = run.shared; result[1] = run.left_only; result[2] = run.right_only;
-  if(records && (result[1] > left_capacity || result[2] > right_capacity)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "record buffers smaller than result[1] / result[2]"); }
-  return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("compareKMers: ") + e.what()); }
-}
-
-} // namespace
-
-extern "C" int gcsa2_compare_kmers(const gcsa2_index* left, const gcsa2_index* right, uint64_t k, int include_ns, int force,
-                                   uint64_t* result)
-{
-  return compare_kmers_impl(left, right, k, include_ns, force, result, nullptr, 0, nullptr, 0, false);
-}
-
-extern "C" int gcsa2_compare_kmers_records(const gcsa2_index* left, const gcsa2_index* right, uint64_t k, int include_ns, int force,
-                                           uint64_t* result, uint64_t* left_records, uint64_t left_capacity,
-                                           uint64_t* right_records, uint64_t right_capacity)
-{
-  if((left_records == nullptr && left_capacity > 0) || (right_records == nullptr && right_capacity > 0)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null record buffer"); }
-  return compare_kmers_impl(left, right, k, include_ns, force, result, left_records, left_capacity, right_records, right_capacity, true);
 }
 
 // ---- `.gcsa` / `.lcp` files as written by GCSA::serialize / LCPArray::serialize ---------------------
@@ -5985,140 +5665,8 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
 
 }  // extern "C"
 
-// ==== index k-mer spectrum: the k-mers of the index itself, binned, listed or summed per graph node (kernels_spectrum.hpp) ====
-namespace {
-
-// what the three calls refuse before any device is touched
-int spectrum_checks(const gcsa2_index* ix, u64 k, int flags, int known_flags, const char* name)
-{
-  CHECK_INDEX(ix);
-  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": k must be at least 1"); }
-  if((flags & ~known_flags) != 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": unknown flags"); }
-  if(ix->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": alphabet too small for countKMers"); }
-  return GCSA2_OK;
-}
-
-int spectrum_counters(const gcsa2_index* ix, int flags, const char* name)
-{
-  if((flags & GCSA2_SPECTRUM_COUNTS) != 0 && !ix->img.has_counters)
-  {
-    return fail(GCSA2_ERR_MISSING_COMPONENT, std::string(name) + ": GCSA2_SPECTRUM_COUNTS on an index that was created without counters");
-  }
-  return GCSA2_OK;
-}
-
-// countKMers returns 0 for these (algorithms.cpp:391-395); so does every output here
-inline bool spectrum_nothing(const gcsa2_index* ix, u64 k, int force) { return (k > ix->order && !force) || ix->img.n == 0; }
-
-inline u32 spectrum_limit(const gcsa2_index* ix, int include_ns) { return u32(include_ns ? ix->img.sigma - 2 : ix->img.fast_chars); }
-
-}  // namespace
-
-extern "C" {
-
-int gcsa2_kmer_spectrum(const gcsa2_index* ix, uint64_t k, int include_ns, int force, int flags, uint64_t* histogram, uint64_t n_hist,
-                        gcsa2_spectrum_stats* stats)
-{
-  int rc = spectrum_checks(ix, k, flags, GCSA2_SPECTRUM_COUNTS, "kmer_spectrum");
-  if(rc != GCSA2_OK) { return rc; }
-  if(histogram == nullptr && n_hist > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_spectrum: histogram is NULL with n_hist > 0"); }
-  rc = spectrum_counters(ix, flags, "kmer_spectrum");
-  if(rc != GCSA2_OK) { return rc; }
-  try {   // no C++ exception may cross the C boundary
-  g_error.clear();
-  for(u64 i = 0; i < n_hist; i++) { histogram[i] = 0; }
-  gcsa2_spectrum_stats sums{};
-  if(stats != nullptr) { *stats = sums; }
-  if(spectrum_nothing(ix, k, force)) { return GCSA2_OK; }
-  DeviceGuard guard(ix->device);
-  DBuf<unsigned long long> stat, hist;
-  HIP_TRY(stat.alloc(SPEC_WORDS));
-  if(n_hist > 0) { HIP_TRY(hist.alloc(n_hist)); HIP_TRY(hipMemset(hist.p, 0, n_hist * sizeof(unsigned long long))); }
-  SpectrumRun run{ix, nullptr, spectrum_limit(ix, include_ns), k, SPEC_HISTOGRAM, int((flags & GCSA2_SPECTRUM_COUNTS) != 0), stat.p,
-                  (n_hist > 0 ? hist.p : nullptr), n_hist, 0, 0, nullptr};
-  rc = spectrum_walk(run);
-  if(rc != GCSA2_OK) { return rc; }
-  unsigned long long host_stat[SPEC_WORDS];
-  HIP_TRY(hipMemcpy(host_stat, stat.p, sizeof(host_stat), hipMemcpyDeviceToHost));
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the histogram is copied as it stands");
-  if(n_hist > 0) { HIP_TRY(hipMemcpy(histogram, hist.p, n_hist * sizeof(u64), hipMemcpyDeviceToHost)); }
-  sums.kmers = host_stat[SPEC_KMERS]; sums.nodes = host_stat[SPEC_NODES]; sums.occurrences = host_stat[SPEC_OCCURRENCES];
-  sums.unique = host_stat[SPEC_UNIQUE]; sums.max_value = host_stat[SPEC_MAX];
-  if(stats != nullptr) { *stats = sums; }
-  return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_spectrum: ") + e.what()); }
-}
-
-int gcsa2_list_kmers(const gcsa2_index* ix, uint64_t k, int include_ns, int force, int flags, uint64_t min_value, uint64_t max_value,
-                     gcsa2_index_kmer* records, uint64_t capacity, uint64_t* total)
-{
-  int rc = spectrum_checks(ix, k, flags, GCSA2_SPECTRUM_COUNTS, "list_kmers");
-  if(rc != GCSA2_OK) { return rc; }
-  if(total == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: total is NULL"); }
-  if(k > 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: k must be at most 64 (the key holds 64 steps)"); }
-  if(max_value != 0 && min_value > max_value) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: min_value exceeds max_value"); }
-  if(records == nullptr && capacity > 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "list_kmers: records is NULL with capacity > 0"); }
-  rc = spectrum_counters(ix, flags, "list_kmers");
-  if(rc != GCSA2_OK) { return rc; }
-  try {   // no C++ exception may cross the C boundary
-  g_error.clear();
-  *total = 0;
-  if(spectrum_nothing(ix, k, force)) { return GCSA2_OK; }
-  static_assert(sizeof(gcsa2_index_kmer) == 8 * sizeof(u64), "gcsa2_index_kmer is eight words");
-  DeviceGuard guard(ix->device);
-  DBuf<unsigned long long> stat;
-  HIP_TRY(stat.alloc(SPEC_WORDS));
-  u64 listed = 0;
-  SpectrumRun run{ix, nullptr, spectrum_limit(ix, include_ns), k, SPEC_LIST, int((flags & GCSA2_SPECTRUM_COUNTS) != 0), stat.p, nullptr, 0,
-                  min_value, max_value, nullptr};
-  run.sink = [&](const u64* d_recs, const u64*, u64 m) -> int     // a piece that no longer fits is counted, not copied
-  {
-    if(listed + m <= capacity) { HIP_TRY(hipMemcpy(records + listed, d_recs, m * sizeof(gcsa2_index_kmer), hipMemcpyDeviceToHost)); }
-    listed += m;
-    return GCSA2_OK;
-  };
-  rc = spectrum_walk(run);
-  if(rc != GCSA2_OK) { return rc; }
-  *total = listed;
-  if(listed > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "list_kmers: capacity is smaller than *total"); }
-  return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_list_kmers: ") + e.what()); }
-}
-
-int gcsa2_index_kmer_support_device(const gcsa2_index* ix, uint64_t k, int include_ns, int force, uint64_t hit_max, uint64_t shift, int flags,
-                                    uint64_t* d_support, uint64_t n_bins, gcsa2_support_stats* stats, void* stream)
-{
-  CHECK_INDEX(ix);
-  if(k == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "index_kmer_support: k must be at least 1"); }
-  if(ix->img.sigma < 3) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "index_kmer_support: alphabet too small for countKMers"); }
-  int rc = support_checks(ix, shift, flags, d_support, n_bins, "d_support");
-  if(rc != GCSA2_OK) { return rc; }
-  gcsa2_support_stats sums{};
-  if(spectrum_nothing(ix, k, force)) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  g_error.clear();
-  DeviceGuard guard(ix->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  DBuf<unsigned long long> stat;
-  HIP_TRY(stat.alloc(SPEC_WORDS));
-  SpectrumRun run{ix, st, spectrum_limit(ix, include_ns), k, SPEC_SEEDS, 1, stat.p, nullptr, 0, 0, 0, nullptr};
-  run.sink = [&](const u64* d_recs, const u64* d_counts, u64 m) -> int       // one piece: the core of gcsa2_seed_support_device
-  {
-    gcsa2_support_stats piece{};
-    Scratch scratch(ix, st);
-    const int piece_rc = support_tail(ix, d_recs, 5, d_counts, nullptr, m, hit_max, shift, flags, d_support, n_bins, &piece, scratch, st);
-    if(piece_rc != GCSA2_OK) { return piece_rc; }
-    sums.windows += m; sums.found += piece.found; sums.counted += piece.counted; sums.distinct += piece.distinct;
-    sums.values += piece.values; sums.added += piece.added; sums.dropped += piece.dropped;
-    return GCSA2_OK;
-  };
-  rc = spectrum_walk(run);
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_index_kmer_support_device: ") + e.what()); }
-}
-
-}  // extern "C"
+// ==== the index-side k-mer calls: countKMers, compareKMers, the index k-mer spectrum (one walk of one search tree) ====
+#include "host_kmers.hpp"
 
 // ==== k-mer classes: per read, the votes of its k-mers (or any seed records) over classes of graph nodes (kernels_classes.hpp) ====
 namespace {

@@ -1445,149 +1445,6 @@ __global__ __launch_bounds__(TPB) void k_sort_small(const u64* __restrict__ raw_
   if(__ballot(dups != 0) != 0) { report_dups(totals, 1u, threadIdx.x & 63); }      // (uniform)
 }
 
-// ---- countKMers frontier expansion (src/algorithms.cpp:364-421) -------------------------------
-// One lane per search state (a non-empty range at depth d): its children are LF_fast / LF_all of
-// the range (src/gcsa.cpp:742-798) for comps 1..limit; non-empty children are appended to `out`
-// (wave-aggregated atomic slot allocation) or, when out == nullptr, only counted.
-constexpr int KMER_CHUNK = 4;       // comps per batch of independent block loads (the fast characters)
-
-__global__ __launch_bounds__(TPB) void k_kmer_expand(DevImage img, const u64* __restrict__ in, u64 n_in, u32 limit,
-                                                     u64* __restrict__ out, unsigned long long* __restrict__ counter)
-{
-  __shared__ WgSlots slots;
-  u64 q = u64(blockIdx.x) * TPB + threadIdx.x;
-  const u32 lane = threadIdx.x & 63;
-  const u64 below = (u64(1) << lane) - 1;
-  bool live = q < n_in;
-  ulonglong2 r = live ? reinterpret_cast<const ulonglong2*>(in)[q] : make_ulonglong2(1, 0);
-  for(u32 c0 = 1; c0 <= limit; c0 += KMER_CHUNK)
-  {
-    u64 csp[KMER_CHUNK], cep[KMER_CHUNK], mask[KMER_CHUNK];
-    lf_children<KMER_CHUNK>(img, c0, limit, live, r.x, r.y, csp, cep);
-    u32 wave_count = 0;
-#pragma unroll
-    for(int j = 0; j < KMER_CHUNK; j++)
-    {
-      mask[j] = __ballot(live && c0 + u32(j) <= limit && !range_empty(csp[j], cep[j]));
-      wave_count += u32(__popcll(mask[j]));
-    }
-    u64 slot = wg_reserve(slots, counter, wave_count);
-#pragma unroll
-    for(int j = 0; j < KMER_CHUNK; j++)
-    {
-      if(out != nullptr && ((mask[j] >> lane) & 1))
-      {
-        reinterpret_cast<ulonglong2*>(out)[slot + __popcll(mask[j] & below)] = make_ulonglong2(csp[j], cep[j]);
-      }
-      slot += __popcll(mask[j]);
-    }
-  }
-}
-
-// ---- compareKMers frontier expansion (src/algorithms.cpp:505-616) ------------------------------
-// A state is a pair of ranges, one per index; a child survives if it is non-empty in at least one
-// index.  The two images are read through pointers (two DevImage values would not fit the 4 KB
-// kernel-argument segment).  final != 0: classify the children instead of storing them:
-// counters[1] += shared, counters[2] += left only, counters[3] += right only.
-// KMerComparisonState::set (algorithms.cpp:451-457): comp of extension step i at bits [3i, 3i + 3).
-// (The reference also evaluates `comp >> (64 - bit)` for bit == 0, a shift by the word size; the intended
-// "|= 0 unless the comp straddles two words" is what is restated here.)
-__device__ __forceinline__ void kmer_set(u64* kmer, u32 i, u64 comp)
-{
-  u32 offset = (i * 3) >> 6, bit = (i * 3) & 63;
-  kmer[offset] |= comp << bit;
-  if(bit > 61) { kmer[offset + 1] |= comp >> (64 - bit); }
-}
-
-// mode 0: expand (children appended to out / out_keys, counters[0] = number of children)
-// mode 1: classify the children: counters[1] += shared, counters[2] += left only, counters[3] += right only
-// mode 2: like 1, and the left-only / right-only children are written as 8-u64 KMerComparisonState
-//         records (left range, right range, k, kmer[3]) to left_records / right_records
-__global__ __launch_bounds__(TPB) void k_kmer_compare(const DevImage* __restrict__ left, const DevImage* __restrict__ right,
-                                                      const u64* __restrict__ in, const u64* __restrict__ in_keys, u64 n_in,
-                                                      u32 limit, u32 depth, int mode,
-                                                      u64* __restrict__ out, u64* __restrict__ out_keys,
-                                                      unsigned long long* __restrict__ counters,
-                                                      u64* __restrict__ left_records, u64* __restrict__ right_records)
-{
-  __shared__ WgSlots slots;
-  u64 q = u64(blockIdx.x) * TPB + threadIdx.x;
-  const u32 lane = threadIdx.x & 63;
-  const u64 below = (u64(1) << lane) - 1;
-  bool live = q < n_in;
-  ulonglong2 l = make_ulonglong2(1, 0), r = make_ulonglong2(1, 0);
-  u64 key[3] = {0, 0, 0};
-  if(live)
-  {
-    l = reinterpret_cast<const ulonglong2*>(in)[2 * q]; r = reinterpret_cast<const ulonglong2*>(in)[2 * q + 1];
-    if(in_keys != nullptr) { key[0] = in_keys[3 * q]; key[1] = in_keys[3 * q + 1]; key[2] = in_keys[3 * q + 2]; }
-  }
-  unsigned long long shared_total = 0;          // mode 1 / 2: k-mers in both indexes, per wave
-  for(u32 c0 = 1; c0 <= limit; c0 += KMER_CHUNK)
-  {
-    u64 lcsp[KMER_CHUNK], lcep[KMER_CHUNK], rcsp[KMER_CHUNK], rcep[KMER_CHUNK];
-    lf_children<KMER_CHUNK>(*left, c0, limit, live, l.x, l.y, lcsp, lcep);
-    lf_children<KMER_CHUNK>(*right, c0, limit, live, r.x, r.y, rcsp, rcep);
-    u64 lmask[KMER_CHUNK], rmask[KMER_CHUNK];      // children that are non-empty on the left / right
-    u32 any_count = 0, lonly_count = 0, ronly_count = 0;
-#pragma unroll
-    for(int j = 0; j < KMER_CHUNK; j++)
-    {
-      const bool active = live && c0 + u32(j) <= limit;
-      lmask[j] = __ballot(active && !range_empty(lcsp[j], lcep[j]));
-      rmask[j] = __ballot(active && !range_empty(rcsp[j], rcep[j]));
-      any_count += u32(__popcll(lmask[j] | rmask[j]));
-      lonly_count += u32(__popcll(lmask[j] & ~rmask[j]));
-      ronly_count += u32(__popcll(rmask[j] & ~lmask[j]));
-      shared_total += (unsigned long long)__popcll(lmask[j] & rmask[j]);
-    }
-    if(mode == 0)
-    {
-      u64 slot = wg_reserve(slots, counters, any_count);
-#pragma unroll
-      for(int j = 0; j < KMER_CHUNK; j++)
-      {
-        const u64 mask = lmask[j] | rmask[j];
-        if(out != nullptr && ((mask >> lane) & 1))
-        {
-          const u64 at = slot + __popcll(mask & below);
-          reinterpret_cast<ulonglong2*>(out)[2 * at] = make_ulonglong2(lcsp[j], lcep[j]);
-          reinterpret_cast<ulonglong2*>(out)[2 * at + 1] = make_ulonglong2(rcsp[j], rcep[j]);
-          if(out_keys != nullptr)
-          {
-            u64 child[3] = {key[0], key[1], key[2]};
-            kmer_set(child, depth, c0 + u32(j));
-            out_keys[3 * at] = child[0]; out_keys[3 * at + 1] = child[1]; out_keys[3 * at + 2] = child[2];
-          }
-        }
-        slot += __popcll(mask);
-      }
-      continue;
-    }
-    u64 lslot = wg_reserve(slots, counters + 2, lonly_count);
-    u64 rslot = wg_reserve(slots, counters + 3, ronly_count);
-    if(mode == 2)
-    {
-#pragma unroll
-      for(int j = 0; j < KMER_CHUNK; j++)
-      {
-        const u64 lonly = lmask[j] & ~rmask[j], ronly = rmask[j] & ~lmask[j];
-        const bool mine_left = (lonly >> lane) & 1, mine_right = (ronly >> lane) & 1;
-        if(mine_left || mine_right)
-        {
-          u64 child[3] = {key[0], key[1], key[2]};
-          kmer_set(child, depth, c0 + u32(j));
-          u64* rec = (mine_left ? left_records + 8 * (lslot + __popcll(lonly & below)) : right_records + 8 * (rslot + __popcll(ronly & below)));
-          rec[0] = lcsp[j]; rec[1] = lcep[j]; rec[2] = rcsp[j]; rec[3] = rcep[j]; rec[4] = u64(depth) + 1;
-          rec[5] = child[0]; rec[6] = child[1]; rec[7] = child[2];
-        }
-        lslot += __popcll(lonly); rslot += __popcll(ronly);
-      }
-    }
-  }
-  if(mode != 0) { wg_reserve(slots, counters + 1, u32(shared_total)); }
-}
-
 // ---- locate ------------------------------------------------------------------------------
 
 // per query: number of path nodes to walk and number of values before deduplication

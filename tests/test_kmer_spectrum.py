@@ -1,4 +1,4 @@
-"""Index k-mer spectrum (gcsa2_kmer_spectrum / gcsa2_list_kmers / gcsa2_index_kmer_support_device, kernels_spectrum.hpp): the
+"""Index k-mer spectrum (gcsa2_kmer_spectrum / gcsa2_list_kmers / gcsa2_index_kmer_support_device, kernels_kmers.hpp): the
 k-mers of the index itself, binned by value, listed, or summed per bin of located values.  The expectations are the CPU
 oracle's alone: a Python walk over OracleIndex.LF_fast / LF_all from the root gives the states of depth k and their keys,
 count_batch their values, and the Folded / tally helpers of test_kmer_support (locate_batch once per distinct range) the
