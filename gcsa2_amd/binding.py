@@ -59,6 +59,7 @@ EXPORTS = [
     "gcsa2_match_breaks_bounded_device", "gcsa2_match_breaks_bounded_batch", "gcsa2_mem_hits_bounded_device", "gcsa2_mem_hits_bounded_batch", "gcsa2_sub_mem_hits_device", "gcsa2_sub_mem_hits_batch",
     "gcsa2_extend_device", "gcsa2_extend_batch", "gcsa2_kmer_windows_device", "gcsa2_kmer_windows_batch",
     "gcsa2_kmer_hits_device", "gcsa2_kmer_hits_batch",
+    "gcsa2_minimizers_device", "gcsa2_minimizers_batch", "gcsa2_minimizer_hits_device", "gcsa2_minimizer_hits_batch",
     "gcsa2_capped_seeds_device", "gcsa2_capped_seeds_batch",
     "gcsa2_kmer_support_device", "gcsa2_kmer_support_batch", "gcsa2_seed_support_device",
     "gcsa2_kmer_spectrum", "gcsa2_list_kmers", "gcsa2_index_kmer_support_device",
@@ -187,6 +188,10 @@ def load_library():
     L.gcsa2_kmer_windows_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, C.c_int, vp, vp, vp, vp, u64, u64p]
     L.gcsa2_kmer_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_kmer_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p]
+    L.gcsa2_minimizers_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, vp, vp, u64, u64p, vp]
+    L.gcsa2_minimizers_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, vp, vp, u64, u64p]
+    L.gcsa2_minimizer_hits_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
+    L.gcsa2_minimizer_hits_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_kmer_support_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp, vp]
     L.gcsa2_kmer_support_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, vp]
     L.gcsa2_seed_support_device.argtypes = [vp, vp, u64, vp, u64, u64, C.c_int, vp, u64, vp, vp]
@@ -608,6 +613,114 @@ class GCSA:
         rc = self._L.gcsa2_kmer_hits_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), over, d_profiles or None,
                                             d_seed_offsets, d_seeds or None, int(seed_capacity), C.byref(total_m), d_hit_offsets, d_hits or None,
                                             int(hit_capacity), C.byref(total_h), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_m.value, total_h.value)
+            raise err
+        return total_m.value, total_h.value
+
+    def minimizers_batch(self, patterns, offsets, k, w, hash_seed=0, out=None):
+        """The (w, k)-minimizers of every read of a batch in host memory (gcsa2_minimizers_batch): (min_offsets (reads + 1),
+        minimizers (total, 2) = {position, hash}).  Of every w consecutive valid k-mers of a read the one with the smallest
+        (hash, position) is selected, hash = SplitMix64's finaliser of the 2-bit packed k-mer ^ hash_seed; a run of fewer than w
+        valid k-mers gives one.  Needs nothing of the index but its alphabet.  The records are sized from a first refusal.
+        `out` = (min_offsets, minimizers) arrays of the caller; too small ones raise BUFFER_TOO_SMALL with `needed`."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        total = C.c_uint64()
+
+        def call(moff, mins):
+            assert moff.dtype == np.uint64 and moff.shape[0] >= n + 1 and mins.dtype == np.uint64 and mins.flags.c_contiguous and mins.shape[1] == 2
+            return self._L.gcsa2_minimizers_batch(self._h, _p8(patterns), _p64(offsets), n, int(k), int(w), int(hash_seed), moff.ctypes.data,
+                                                  mins.ctypes.data, mins.shape[0], C.byref(total))
+
+        if out is not None:
+            moff, mins = out
+            rc = call(moff, mins)
+        else:
+            moff = np.zeros(n + 1, dtype=np.uint64)
+            mins = np.zeros((0, 2), dtype=np.uint64)
+            rc = call(moff, mins)
+            if rc == STATUS_BUFFER_TOO_SMALL and total.value > 0:
+                mins = np.zeros((total.value, 2), dtype=np.uint64)
+                rc = call(moff, mins)
+        if rc == STATUS_BUFFER_TOO_SMALL:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = total.value
+            raise err
+        _check(rc)
+        return moff[: n + 1], mins[: total.value]
+
+    def minimizers_device(self, d_patterns, d_offsets, n_patterns, k, w, hash_seed, d_min_offsets, d_minimizers, capacity, stream=0):
+        """gcsa2_minimizers_device on caller-owned device buffers (raw pointers): d_min_offsets n_patterns + 1 u64, d_minimizers
+        `capacity` records of two u64 {position, hash} (0 / None with capacity 0: a sizing call).  Complete on return.  Returns
+        the number of minimizers; raises Gcsa2Error with `.needed` = that number otherwise (BUFFER_TOO_SMALL: more than
+        `capacity`; the offsets are complete then)."""
+        needed = C.c_uint64()
+        rc = self._L.gcsa2_minimizers_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(w), int(hash_seed), d_min_offsets,
+                                             d_minimizers or None, int(capacity), C.byref(needed), stream)
+        if rc != 0:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = needed.value
+            raise err
+        return needed.value
+
+    def minimizer_hits_batch(self, patterns, offsets, k, w, hash_seed=0, hit_max=0, sample=False, profiles=False, out=None):
+        """The minimizers of every read that occur, as seeds with counts and positions (gcsa2_minimizer_hits_batch):
+        kmer_hits_batch with the (w, k)-minimizers of minimizers_batch as the windows, in the place of every stride-th one.
+        Returns (seed_offsets (reads + 1), seeds (total, 5) = {position, length = k, sp, ep, count}, hit_offsets (total + 1),
+        hits[, profiles (reads, 4)]); profiles' windows are the minimizers of the read.  The buffers are sized from a first
+        refusal.  `out` = (seed_offsets, seeds, hit_offsets, hits) arrays of the caller; too small ones raise BUFFER_TOO_SMALL
+        with `needed` = (seeds, hits)."""
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        over = 1 if sample else 0
+        prof = np.zeros((n, 4), dtype=np.uint64) if profiles else None
+        total_m, total_h = C.c_uint64(), C.c_uint64()
+
+        def call(soff, seeds, hoff, hits):
+            assert soff.dtype == np.uint64 and soff.shape[0] >= n + 1 and seeds.dtype == np.uint64 and seeds.flags.c_contiguous
+            assert seeds.shape[1] == 5 and hoff.dtype == np.uint64 and hoff.shape[0] >= seeds.shape[0] + 1 and hits.dtype == np.uint64
+            return self._L.gcsa2_minimizer_hits_batch(self._h, _p8(patterns), _p64(offsets), n, int(k), int(w), int(hash_seed), int(hit_max), over,
+                                                      None if prof is None else prof.ctypes.data, soff.ctypes.data, seeds.ctypes.data,
+                                                      seeds.shape[0], C.byref(total_m), hoff.ctypes.data, hits.ctypes.data, hits.shape[0],
+                                                      C.byref(total_h))
+
+        if out is not None:
+            soff, seeds, hoff, hits = out
+            rc = call(soff, seeds, hoff, hits)
+        else:
+            mcap, hcap = 0, 0
+            soff = np.zeros(n + 1, dtype=np.uint64)
+            for _ in range(2):
+                seeds = np.zeros((mcap, 5), dtype=np.uint64)
+                hoff = np.zeros(mcap + 1, dtype=np.uint64)
+                hits = np.zeros(hcap, dtype=np.uint64)
+                rc = call(soff, seeds, hoff, hits)
+                if rc != STATUS_BUFFER_TOO_SMALL:
+                    break
+                mcap, hcap = max(mcap, total_m.value), max(hcap, total_h.value)
+        if rc == STATUS_BUFFER_TOO_SMALL:
+            err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+            err.needed = (total_m.value, total_h.value)
+            raise err
+        _check(rc)
+        m, h = total_m.value, total_h.value
+        res = (soff[: n + 1], seeds[:m], hoff[: m + 1], hits[:h])
+        return res + (prof,) if profiles else res
+
+    def minimizer_hits_device(self, d_patterns, d_offsets, n_patterns, k, w, hash_seed, hit_max, sample, d_profiles, d_seed_offsets, d_seeds,
+                              seed_capacity, d_hit_offsets, d_hits, hit_capacity, stream=0):
+        """gcsa2_minimizer_hits_device on caller-owned device buffers (raw pointers), the buffers as for kmer_hits_device.
+        `sample`: a bool, or the `over` policy as an int.  Complete on return.  Returns (seeds, hits); raises Gcsa2Error
+        (BUFFER_TOO_SMALL, `.needed` = (seeds, hits)) when a buffer is too small."""
+        total_m, total_h = C.c_uint64(), C.c_uint64()
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        rc = self._L.gcsa2_minimizer_hits_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(w), int(hash_seed), int(hit_max), over,
+                                                 d_profiles or None, d_seed_offsets, d_seeds or None, int(seed_capacity), C.byref(total_m),
+                                                 d_hit_offsets, d_hits or None, int(hit_capacity), C.byref(total_h), stream)
         if rc != 0:
             err = Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
             err.needed = (total_m.value, total_h.value)

@@ -14,6 +14,8 @@
 //                       k_locate_*            GCSA::locate(range), locateInternal, removeDuplicates
 //                                                                        src/gcsa.cpp:827-842, 880-896, utils.h:350-357
 //   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
+//   kernels_minimizers.hpp k_minimizers      the (w, k)-minimizers of every read (gcsa2_minimizers_device)
+//                       k_minimizer_seeds     k_kmer_seeds over the selected windows (gcsa2_minimizer_hits_device)
 //   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
 //                       k_kmer_seeds          the same search, emitting the found windows as seed records (gcsa2_kmer_hits_device)
 //                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
@@ -59,6 +61,7 @@ using namespace g2;
 #include "kernels_locate_max.hpp"
 #include "kernels_mem.hpp"
 #include "kernels_windows.hpp"
+#include "kernels_minimizers.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_submem.hpp"
 #include "kernels_seeds.hpp"
@@ -4958,8 +4961,10 @@ int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
 // short.  attempts == 2 (capacity is a caller's guess): a short area is re-made at m and the search runs again, so each
 // run zeroes what it left behind (`prof`, found[spans]) and the area is taken after the owners are on their way; attempts ==
 // 1 (capacity == total): the area first, one run.  One host round trip per run.
+// `mins` (gcsa2_minimizer_hits_device): the windows are those of this list, woff its offsets per read; `stride` is not used.
 int kmer_seed_search(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
-                     const u64* woff, u64 total, u64 capacity, gcsa2_kmer_profile* prof, int attempts, hipStream_t st, SeedEmit& emit, u64& m)
+                     const u64* woff, u64 total, u64 capacity, gcsa2_kmer_profile* prof, int attempts, hipStream_t st, SeedEmit& emit, u64& m,
+                     const gcsa2_minimizer* mins = nullptr)
 {
   const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
   static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
@@ -4990,7 +4995,12 @@ int kmer_seed_search(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_p
     HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
     if(rerun) { HIP_TRY(hipMemsetAsync(emit.found + spans, 0, sizeof(u32), st)); }
     if(prof != nullptr) { HIP_TRY(hipMemsetAsync(prof, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
-    if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
+    if(mins != nullptr)
+    {
+      if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_minimizer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, mins, woff, owners, total, prof, emit); }
+      else { hipLaunchKernelGGL((k_minimizer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, mins, woff, owners, total, prof, emit); }
+    }
+    else if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_kmer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
     else { hipLaunchKernelGGL((k_kmer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, stride, woff, owners, total, prof, emit); }
     LAUNCH_CHECK("k_kmer_seeds");
     HIP_TRY(hipMemcpyAsync(&m, emit.cursor, sizeof(u64), hipMemcpyDeviceToHost, st));
@@ -5106,14 +5116,14 @@ int kmer_hits_checks(const gcsa2_index* ix, u64 k, u64 stride, int over, const u
 // number of seeds (twice when the arrival area was too small for them), those of the shared tail, the end.
 // Scratch: per read the window offsets and, if asked for, the profiles (the caller's only once everything fits); per 64
 // windows the owner entry and 16 bytes of SeedEmit; the rest per seed.
-int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max, int over,
-                   gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
-                   u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+// kmer_hits_found is everything behind the plan of the windows: `total` windows with the offsets `woff` per read, at j stride
+// or, with `mins` (gcsa2_minimizer_hits_device), at the positions of that list.
+int kmer_hits_found(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
+                    const u64* woff, u64 total, const gcsa2_minimizer* mins, u64 hit_max, int over,
+                    gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
+                    u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
 {
-  Scratch scratch(ix, st);
-  u64 *woff = nullptr, total = 0;
-  int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_hits", st, woff, total);
-  if(rc != GCSA2_OK) { return rc; }
+  int rc = GCSA2_OK;
   // no seed: zeroed offsets, the profiles are their window numbers
   auto nothing_found = [&](const gcsa2_kmer_profile* prof) -> int
   {
@@ -5135,7 +5145,7 @@ int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint6
   SeedEmit emit{};
   u64 m = 0;
   if(d_profiles != nullptr) { HIP_TRY(scratch.get(prof, n_patterns)); }
-  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, std::min(seed_capacity, total), prof, 2, st, emit, m);
+  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, std::min(seed_capacity, total), prof, 2, st, emit, m, mins);
   if(rc != GCSA2_OK) { return rc; }
   if(m > emit.capacity) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "kmer_hits: two runs of the search disagree on the number of seeds"); }
   *total_seeds = m;
@@ -5161,6 +5171,18 @@ int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint6
   HIP_TRY(hipStreamSynchronize(st));
   scratch.settled = true;
   return GCSA2_OK;
+}
+
+int kmer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, u64 hit_max, int over,
+                   gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
+                   u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *woff = nullptr, total = 0;
+  const int rc = window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_hits", st, woff, total);
+  if(rc != GCSA2_OK) { return rc; }
+  return kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, nullptr, hit_max, over, d_profiles, d_seed_offsets, d_seeds,
+                         seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
 }
 
 }  // namespace
@@ -5237,6 +5259,267 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const 
   return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, sizeof(gcsa2_kmer_profile), profiles, seed_offsets, seeds, seed_capacity,
                            total_seeds, hit_offsets, hits, hit_capacity, total_hits);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== minimizers: the (w, k)-minimizers of every read, alone and as the windows of the k-mer hits (kernels_minimizers.hpp) ====
+namespace {
+
+// what all four forms refuse before any device is touched
+int minimizers_checks(const gcsa2_index* ix, u64 k, u64 w, const u64* total)
+{
+  CHECK_INDEX(ix);
+  if(total == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(k == 0 || k > GCSA2_MINIMIZER_MAX_K) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "minimizers: k must be 1 .. 32"); }
+  if(w == 0 || w > GCSA2_MINIMIZER_MAX_W) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "minimizers: w must be 1 .. 64"); }
+  return GCSA2_OK;
+}
+
+// then the over-cap policy and the components the hits need (no LCP array)
+int minimizer_hits_checks(const gcsa2_index* ix, u64 k, u64 w, int over, const u64* total_seeds, const u64* total_hits)
+{
+  const int rc = minimizers_checks(ix, k, w, total_seeds);
+  if(rc != GCSA2_OK) { return rc; }
+  if(total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(over != GCSA2_MEM_OVER_SKIP && over != GCSA2_MEM_OVER_SAMPLE)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "minimizer_hits: unknown over-cap policy (GCSA2_MEM_OVER_SKIP or GCSA2_MEM_OVER_SAMPLE)");
+  }
+  return locate_checks(ix, 0);
+}
+
+// The selection (0 < n_patterns < 2^32): a counting pass, the scan into the offsets (n_patterns + 1 entries, in `moff_or_null` or in
+// scratch), one host round trip for the number of minimizers and of stride-1 windows, then the same pass again placing the
+// records -- into scratch (to_scratch), or into `out` if they fit in `capacity` (else GCSA2_ERR_BUFFER_TOO_SMALL with the
+// offsets complete and no record written).  The stream is idle when this returns a refusal; after the placing pass it is not.
+int minimizer_select(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w,
+                     u64 hash_seed, u64* moff_or_null, bool to_scratch, gcsa2_minimizer* out, u64 capacity, const char* name, hipStream_t st,
+                     u64*& moff, gcsa2_minimizer*& mins, u64& total)
+{
+  u64 *sizes = nullptr, *windows = nullptr;
+  char *scan_tmp = nullptr, *sum_tmp = nullptr;
+  moff = moff_or_null;
+  mins = out;
+  total = 0;
+  HIP_TRY(scratch.get(sizes, n_patterns + 1));
+  HIP_TRY(scratch.get(windows, 1));
+  if(moff == nullptr) { HIP_TRY(scratch.get(moff, n_patterns + 1)); }
+  const dim3 grid(unsigned(std::min<u64>(n_patterns, u64(1) << 20)));
+  hipLaunchKernelGGL((k_minimizers<false>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed, sizes,
+                     static_cast<const u64*>(nullptr), static_cast<gcsa2_minimizer*>(nullptr));
+  LAUNCH_CHECK("k_minimizers");
+  size_t scan_bytes = 0, sum_bytes = 0;
+  hipcub::TransformInputIterator<u64, MiniWindowsOf, hipcub::CountingInputIterator<u64>> per_read(hipcub::CountingInputIterator<u64>(0), MiniWindowsOf{d_offsets, k});
+  HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, sum_bytes, per_read, windows, size_t(n_patterns), st));
+  HIP_TRY(scratch.get(sum_tmp, sum_bytes));
+  HIP_TRY(hipcub::DeviceReduce::Sum(sum_tmp, sum_bytes, per_read, windows, size_t(n_patterns), st));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sizes, moff, size_t(n_patterns + 1), st));
+  HIP_TRY(scratch.get(scan_tmp, scan_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, sizes, moff, size_t(n_patterns + 1), st));
+  u64 all_windows = 0;
+  HIP_TRY(hipMemcpyAsync(&total, moff + n_patterns, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&all_windows, windows, sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  if(all_windows >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch"); }
+  if(to_scratch) { HIP_TRY(scratch.get(mins, total)); }
+  else if(total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer buffer too small"); }
+  if(total == 0) { return GCSA2_OK; }
+  scratch.settled = false;
+  hipLaunchKernelGGL((k_minimizers<true>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed,
+                     static_cast<u64*>(nullptr), static_cast<const u64*>(moff), mins);
+  LAUNCH_CHECK("k_minimizers");
+  return GCSA2_OK;
+}
+
+// gcsa2_minimizer_hits_device after its argument checks (0 < n_patterns < 2^32): the selection into scratch, then what
+// gcsa2_kmer_hits_device does behind its window plan, with the minimizers as the windows.
+int minimizer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
+                        u64 hit_max, int over, gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity,
+                        u64* total_seeds, u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *moff = nullptr, total = 0;
+  gcsa2_minimizer* mins = nullptr;
+  const int rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, "minimizer_hits", st,
+                                  moff, mins, total);
+  if(rc != GCSA2_OK) { return rc; }
+  return kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, 1, moff, total, mins, hit_max, over, d_profiles, d_seed_offsets, d_seeds,
+                         seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                            uint64_t hash_seed, uint64_t* d_min_offsets, gcsa2_minimizer* d_minimizers, uint64_t capacity, uint64_t* total,
+                            void* stream)
+{
+  int rc = minimizers_checks(ix, k, w, total);
+  if(rc != GCSA2_OK) { return rc; }
+  *total = 0;
+  if(d_min_offsets == nullptr || (n_patterns > 0 && d_offsets == nullptr) || (d_minimizers == nullptr && capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizers: 2^32 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_min_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  Scratch scratch(ix, st);
+  u64* moff = nullptr;
+  gcsa2_minimizer* mins = nullptr;
+  u64 found = 0;
+  rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, d_min_offsets, false, d_minimizers, capacity, "minimizers", st,
+                        moff, mins, found);
+  *total = found;
+  if(rc != GCSA2_OK) { return rc; }
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizers_device: ") + e.what()); }
+}
+
+// The host form.  The number of minimizers of a piece (for_read_pieces) is not known before it ran, so every piece keeps its
+// offsets and records in host memory and the caller's arrays are put together in read order at the end; the offsets are
+// complete and *total is written whether the records fit or not.
+int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                           uint64_t hash_seed, uint64_t* min_offsets, gcsa2_minimizer* minimizers, uint64_t capacity, uint64_t* total)
+{
+  int rc = minimizers_checks(ix, k, w, total);
+  if(rc != GCSA2_OK) { return rc; }
+  *total = 0;
+  if(min_offsets == nullptr || (n_patterns > 0 && offsets == nullptr) || (minimizers == nullptr && capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizers: 2^32 or more reads in one call; split the batch"); }
+  if(n_patterns == 0) { min_offsets[0] = 0; return GCSA2_OK; }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  if(host_windows(offsets, n_patterns, k, 1) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizers: 2^32 or more windows in one call; split the batch"); }
+  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  struct Piece { std::vector<u64> off; std::vector<gcsa2_minimizer> mins; };
+  std::vector<Piece> done(cut.size() - 1);
+  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
+  {
+    Piece& piece = done[p.c];
+    DBuf<u8> d_pat; DBuf<u64> d_off;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    Scratch scratch(ix, p.stream);
+    u64 *moff = nullptr, found = 0;
+    gcsa2_minimizer* mins = nullptr;
+    const int piece_rc = minimizer_select(ix, scratch, d_pat.p, d_off.p, p.count, k, w, hash_seed, nullptr, true, nullptr, 0, "minimizers", p.stream,
+                                          moff, mins, found);
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    piece.off.resize(p.count + 1); piece.mins.resize(found);
+    hipError_t e = hipMemcpyAsync(piece.off.data(), moff, (p.count + 1) * sizeof(u64), hipMemcpyDeviceToHost, p.stream);
+    if(e == hipSuccess && found > 0) { e = hipMemcpyAsync(piece.mins.data(), mins, found * sizeof(gcsa2_minimizer), hipMemcpyDeviceToHost, p.stream); }
+    if(e == hipSuccess) { e = hipStreamSynchronize(p.stream); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    scratch.settled = true;
+    return true;
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  u64 base = 0;
+  for(u64 c = 0; c + 1 < cut.size(); c++)
+  {
+    const u64 b = cut[c], count = cut[c + 1] - b;
+    for(u64 i = 0; i <= count; i++) { min_offsets[b + i] = done[c].off[i] + base; }
+    base += done[c].mins.size();
+  }
+  *total = base;
+  if(base > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer buffer too small"); }
+  base = 0;
+  for(const Piece& piece : done)
+  {
+    if(!piece.mins.empty()) { std::memcpy(minimizers + base, piece.mins.data(), piece.mins.size() * sizeof(gcsa2_minimizer)); }
+    base += piece.mins.size();
+  }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizers_batch: ") + e.what()); }
+}
+
+int gcsa2_minimizer_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                                uint64_t w, uint64_t hash_seed, uint64_t hit_max, int over, gcsa2_kmer_profile* d_profiles,
+                                uint64_t* d_seed_offsets, gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                                uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  int rc = minimizer_hits_checks(ix, k, w, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(d_seed_offsets == nullptr || d_hit_offsets == nullptr || (n_patterns > 0 && d_offsets == nullptr) || (d_seeds == nullptr && seed_capacity > 0) ||
+     (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer_hits: 2^32 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  return minimizer_hits_core(ix, d_patterns, d_offsets, n_patterns, k, w, hash_seed, hit_max, over, d_profiles, d_seed_offsets, d_seeds, seed_capacity,
+                             total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizer_hits_device: ") + e.what()); }
+}
+
+// The host form (seed_pieces_batch), as gcsa2_kmer_hits_batch: minimizers are per read, so the cut changes nothing.
+int gcsa2_minimizer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                               uint64_t hash_seed, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles, uint64_t* seed_offsets,
+                               gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds, uint64_t* hit_offsets, uint64_t* hits,
+                               uint64_t hit_capacity, uint64_t* total_hits)
+{
+  int rc = minimizer_hits_checks(ix, k, w, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(seed_offsets == nullptr || hit_offsets == nullptr || (n_patterns > 0 && offsets == nullptr) || (seeds == nullptr && seed_capacity > 0) ||
+     (hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer_hits: 2^32 or more reads in one call; split the batch"); }
+  if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  if(host_windows(offsets, n_patterns, k, 1) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer_hits: 2^32 or more windows in one call; split the batch"); }
+  // several pieces: room for every span's minimizer (a bound that the density 2 / (w + 1) stays far below), and an estimate of the hits
+  auto estimate = [&](const ReadPiece& p) -> std::pair<u64, u64>
+  {
+    const u64 windows = host_windows(p.local, p.count, k, 1);
+    if(p.pieces == 1) { return {std::min(seed_capacity, windows), hit_capacity}; }
+    return {windows, 4 * windows};
+  };
+  auto run = [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, u8* d_prof, u64* d_seed_off, gcsa2_mem* d_seeds, u64 rm, u64* m, u64* d_hit_off,
+                 u64* d_hits, u64 rh, u64* h) -> int
+  {
+    return gcsa2_minimizer_hits_device(ix, d_pat, d_off, p.count, k, w, hash_seed, hit_max, over, reinterpret_cast<gcsa2_kmer_profile*>(d_prof), d_seed_off,
+                                       d_seeds, rm, m, d_hit_off, d_hits, rh, h, p.stream);
+  };
+  return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, sizeof(gcsa2_kmer_profile), profiles, seed_offsets, seeds, seed_capacity,
+                           total_seeds, hit_offsets, hits, hit_capacity, total_hits);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizer_hits_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 // text, not a function, so that adding a kernel that shares it leaves the code of the existing ones as it was, instruction
 // for instruction.  In scope: PAIR, COUNTS, the kernel's parameters (img, patterns, offsets, k, stride, window_offsets, owners,
 // total, out, counts, profiles) and, with KMER_WINDOWS_EMIT, `emit` (SeedEmit).  No include guard on purpose.
+// KMER_WINDOWS_POSITION(g), which only k_minimizer_seeds (kernels_minimizers.hpp) defines: where in its read window g of the
+// batch begins, in the place of j * stride; `stride` is then not used.
   __shared__ ulonglong2 stage[TPB2 * 8];
   __shared__ Tables2 t;
   if(threadIdx.x < 2 * MAX_SIGMA) { t.crange[threadIdx.x] = img.crange[threadIdx.x]; }
@@ -30,7 +32,11 @@
     if(j == 0 && profiles != nullptr) { reinterpret_cast<u64*>(profiles + q)[0] = window_offsets[q + 1] - at; }
     if(img.n > 0)                                              // gcsa.h:99 (k >= 1)
     {
+#ifdef KMER_WINDOWS_POSITION
+      p = patterns + offsets[q] + KMER_WINDOWS_POSITION(gid);
+#else
       p = patterns + offsets[q] + j * stride;
+#endif
       const u64 len = k;
       u64 word = 0, word_addr = ~u64(0);                       // pattern bytes from aligned 8-byte words
       auto byte_at = [&](u64 pos) -> u32
@@ -207,7 +213,11 @@
     if(hit && at < emit.capacity)
     {
       ulonglong2* dst = reinterpret_cast<ulonglong2*>(emit.recs + 4 * at);
+#ifdef KMER_WINDOWS_POSITION
+      dst[0] = make_ulonglong2(KMER_WINDOWS_POSITION(gid), k);
+#else
       dst[0] = make_ulonglong2((gid - window_offsets[q]) * stride, k);
+#endif
       dst[1] = make_ulonglong2(sp, ep);
       emit.counts[at] = occ;
     }

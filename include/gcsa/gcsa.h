@@ -319,6 +319,65 @@ public:
     hits.resize(total_hits);
   }
 
+  // The (w, k)-minimizers of every read (gcsa2_minimizers_batch): of every w consecutive valid k-mers the one with the smallest
+  // (hash, position), as records {position, hash}; a run of fewer than w valid k-mers gives one.  Minimizers of read q:
+  // [min_offsets[q], min_offsets[q + 1]).  1 <= k <= 32, 1 <= w <= 64; forward strand only.
+  void minimizers(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w, size_type hash_seed,
+                  std::vector<size_type>& min_offsets, std::vector<gcsa2_minimizer>& minimizers) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    min_offsets.assign(np + 1, 0);
+    minimizers.clear();
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total = 0;
+    for(int attempt = 0; attempt < 2; attempt++)           // the first call sizes the records, unless there are none
+    {
+      const int rc = gcsa2_minimizers_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                            k, w, hash_seed, min_offsets.data(), minimizers.data(), minimizers.size(), &total);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && total > minimizers.size())
+      {
+        minimizers.assign(total, gcsa2_minimizer());
+        continue;
+      }
+      check(rc, "GCSA::minimizers()");
+      break;
+    }
+    minimizers.resize(total);
+  }
+
+  // kmer_hits_batch over the minimizers of every read in the place of every stride-th window (gcsa2_minimizer_hits_batch): the
+  // seeds of a read are its (w, k)-minimizers that find() finds, in ascending position.
+  void minimizer_hits_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                            size_type hash_seed, size_type hit_max, bool sample, std::vector<size_type>& seed_offsets,
+                            std::vector<gcsa2_mem>& seeds, std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    seed_offsets.assign(np + 1, 0);
+    seeds.clear();
+    hits.clear();
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total_seeds = 0, total_hits = 0;
+    for(int attempt = 0; attempt < 2; attempt++)           // the first call sizes the buffers, unless nothing is found
+    {
+      hit_offsets.assign(seeds.size() + 1, 0);
+      const int rc = gcsa2_minimizer_hits_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                                k, w, hash_seed, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, nullptr,
+                                                seed_offsets.data(), seeds.data(), seeds.size(), &total_seeds, hit_offsets.data(), hits.data(),
+                                                hits.size(), &total_hits);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && (total_seeds > seeds.size() || total_hits > hits.size()))
+      {
+        seeds.assign(total_seeds, gcsa2_mem());
+        hits.assign(total_hits, 0);
+        continue;
+      }
+      check(rc, "GCSA::minimizer_hits_batch()");
+      break;
+    }
+    seeds.resize(total_seeds);
+    hit_offsets.resize(total_seeds + 1);
+    hits.resize(total_hits);
+  }
+
   // Frequency-bounded seeds in one call (gcsa2_capped_seeds_batch): from the end of every read the match is extended until it
   // has min_length characters and count(range) <= max_count, emitted as {position, length, sp, ep, count}, and the search
   // starts again behind it; max_length (0: none, a mapper passes order()) cuts an attempt short.  The seeds of a read do not

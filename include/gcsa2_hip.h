@@ -725,6 +725,80 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* index, const uint8_t* patterns, con
                           uint64_t k, uint64_t stride, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles,
                           uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
                           uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
+/* ---- minimizers: the sampled k-mers of every read, alone and as seeds with count() and their positions ----------------------
+ * The k-mer calls above search every stride-th window, and a fixed stride is not shift-invariant: two reads over the same locus
+ * at different offsets pick different k-mers, and an indel moves every later pick.  (w, k)-minimizers -- of every w
+ * consecutive k-mers the one with the smallest hash -- are what k-mer seeders use instead: overlapping reads pick the same
+ * k-mers, and about 2 / (w + 1) of the windows survive.  gcsa2_minimizers_device is the selection alone; it needs nothing of
+ * the index but its alphabet (any image, with or without samples, counters or LCP array).  gcsa2_minimizer_hits_device is
+ * gcsa2_kmer_hits_device with (w, hash_seed) in the place of stride: selection, search, count() and hits in one call.
+ *
+ * DEFINITION.  For read q = P of length L the windows are the stride-1 windows of gcsa2_kmer_windows_device: window j is
+ * P[j, j + k) for 0 <= j < W, W = L - k + 1 (W = 0 if L < k).
+ *   - Codes: code(c) = char2comp[c] - 1 if 1 <= char2comp[c] <= min(4, sigma - 2), else invalid.  A window is VALID if all its k
+ *     characters have a code: with the default alphabet A, C, G, T and their lower-case forms; N, '$', '#' and unknown bytes
+ *     make a window invalid.
+ *   - key(j) = sum over i of code(P[j + i]) << 2 (k - 1 - i): the first character is the most significant, 2 k bits.
+ *     hash(j) = mix64(key(j) ^ hash_seed), mix64 being the SplitMix64 finaliser on 64-bit wrapping arithmetic:
+ *       z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *       return z ^ (z >> 31).
+ *     mix64 is a bijection: distinct k-mers never tie.
+ *   - Spans: of every maximal run [a, b) of consecutive valid windows, r = b - a: if r >= w the spans [s, s + w) for
+ *     a <= s <= b - w; if 1 <= r < w the single span [a, b) -- a short read, or a short stretch between two Ns, still gets one
+ *     minimizer.
+ *   - Selection: each span selects its window with the smallest (hash, position): the leftmost wins a tie.  The minimizers of
+ *     the read are the distinct selected windows in ascending position.  w == 1 selects every valid window.
+ *
+ * gcsa2_minimizers_device: d_min_offsets (n_patterns + 1 entries, the last one *total) is the CSR over reads, the records are
+ * { position = j, hash = hash(j) }.  *total is always the number needed; above `capacity` the call returns
+ * GCSA2_ERR_BUFFER_TOO_SMALL with the offsets complete and nothing written into the records.  d_minimizers == NULL with a
+ * capacity of 0 is a sizing call.
+ *
+ * gcsa2_minimizer_hits_device: the contract of gcsa2_kmer_hits_device, word for word, over the selected windows instead of the
+ * stride windows.  The seeds of a read are its minimizers with a non-empty find(), in ascending position, as { position,
+ * length = k, sp, ep, count }, (sp, ep) bit for bit what gcsa2_find_device returns for the window; the hits follow the hit_max
+ * / GCSA2_MEM_OVER_SKIP / GCSA2_MEM_OVER_SAMPLE rules of gcsa2_mem_hits_device; d_profiles[q] = { windows = the minimizers of
+ * the read, found, nodes, occurrences } over those windows.  Capacities, sizing calls, "nothing written on refusal" and the
+ * limits (fewer than 2^32 reads and fewer than 2^32 stride-1 windows per call) are those of gcsa2_kmer_hits_device; so is the
+ * need for the samples and the counters (GCSA2_ERR_MISSING_COMPONENT) but not for the LCP array.
+ *
+ * GCSA2_ERR_INVALID_ARGUMENT, before any device is touched and with nothing written: k == 0 or k > GCSA2_MINIMIZER_MAX_K,
+ * w == 0 or w > GCSA2_MINIMIZER_MAX_W, an unknown `over`, a NULL index or a NULL total pointer.  n_patterns == 0, no window, no
+ * valid window and no found minimizer are GCSA2_OK: the offsets are zeroed (and d_hit_offsets[0] = 0).  No pattern byte outside
+ * the 8-byte words that hold [d_offsets[0], d_offsets[n_patterns]) is read.  Enqueued on `stream`, complete on return.
+ *
+ * The selection is one wavefront per read in tiles of 64 spans: ballots pack the tile's characters into 2-bit code words and
+ * a bad-character mask, a lane builds its key from two words, and the span minima come from a sparse table in LDS.  It runs
+ * twice (count, scan, place).  The search is the kernel of gcsa2_kmer_hits_device over the list of selected positions.
+ * Device scratch: per read 16 bytes, per minimizer 16 bytes, then that of gcsa2_kmer_hits_device with the minimizers as the windows.
+ *
+ * Out of scope: canonical (both-strand) minimizers, syncmers, w > 64, k > 32, and minimizer forms of the support and class calls. */
+#define GCSA2_MINIMIZER_MAX_K 32
+#define GCSA2_MINIMIZER_MAX_W 64
+typedef struct gcsa2_minimizer { uint64_t position, hash; } gcsa2_minimizer;
+int gcsa2_minimizers_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                            uint64_t k, uint64_t w, uint64_t hash_seed,
+                            uint64_t* d_min_offsets,                       /* n_patterns + 1 */
+                            gcsa2_minimizer* d_minimizers, uint64_t capacity, uint64_t* total, void* stream);
+/* The same for a batch in host memory: offsets[0] == 0, decreasing offsets are refused (GCSA2_ERR_INVALID_ARGUMENT).  A batch
+ * of two pieces' worth of read bytes or more travels in pieces of whole reads (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS); minimizers
+ * are per read, so the result does not depend on the cut.  Complete on return. */
+int gcsa2_minimizers_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                           uint64_t k, uint64_t w, uint64_t hash_seed, uint64_t* min_offsets, gcsa2_minimizer* minimizers,
+                           uint64_t capacity, uint64_t* total);
+int gcsa2_minimizer_hits_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                                uint64_t k, uint64_t w, uint64_t hash_seed, uint64_t hit_max, int over,
+                                gcsa2_kmer_profile* d_profiles,            /* n_patterns, or NULL */
+                                uint64_t* d_seed_offsets,                  /* n_patterns + 1 */
+                                gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                                uint64_t* d_hit_offsets,                   /* seed_capacity + 1 */
+                                uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream);
+/* The host form, as gcsa2_kmer_hits_batch: pieces of whole reads, read order kept; on GCSA2_ERR_BUFFER_TOO_SMALL a batch in
+ * one piece writes nothing, one in pieces leaves the result arrays unspecified.  Complete on return. */
+int gcsa2_minimizer_hits_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                               uint64_t k, uint64_t w, uint64_t hash_seed, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles,
+                               uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                               uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits);
 /* ---- capped seeds: the shortest matches of every read that occur at most max_count times, with their positions -------------
  * A frequency-bounded seed (BWA-MEM's third seeding round, LAST's adaptive seeds): where a read crosses a repeat, MEMs and
  * k-mers end above hit_max and get no positions (GCSA2_MEM_OVER_SKIP) or a sample of them; here the match is extended until it
