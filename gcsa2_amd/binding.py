@@ -34,6 +34,11 @@ TOP_LIMIT = 64              # GCSA2_TOP_LIMIT
 TOP_SLOTS_DEFAULT = 512     # the default of GCSA2_TOP_SLOTS (the test knob of the top-classes calls)
 CLASS_VOTE = np.dtype([("class_id", np.uint64), ("votes", np.uint64)])     # gcsa2_class_vote
 TOP_SUMMARY = np.dtype([("voted", np.uint64), ("total", np.uint64), ("counted", np.uint64)])     # gcsa2_top_summary
+CLUSTER_TOP_LIMIT = 64      # GCSA2_CLUSTER_TOP_LIMIT
+CLUSTER_LDS_DEFAULT = 4096  # the default of GCSA2_CLUSTER_LDS (the test knob of the cluster calls)
+CLUSTER = ("diag_min", "diag_max", "anchors", "starts", "covered", "read_begin", "read_end", "ref_begin")     # gcsa2_cluster
+CLUSTER_SUMMARY = ("anchors", "unplaced", "clusters")     # gcsa2_cluster_summary
+CLUSTER_STATS = ("groups", "invalid_groups", "seeds", "anchors", "unplaced", "clusters", "spilled")     # gcsa2_cluster_stats
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -65,6 +70,8 @@ EXPORTS = [
     "gcsa2_kmer_spectrum", "gcsa2_list_kmers", "gcsa2_index_kmer_support_device",
     "gcsa2_kmer_classes_device", "gcsa2_kmer_classes_batch", "gcsa2_seed_classes_device",
     "gcsa2_kmer_top_classes_device", "gcsa2_kmer_top_classes_batch", "gcsa2_seed_top_classes_device",
+    "gcsa2_seed_clusters_device", "gcsa2_kmer_clusters_device", "gcsa2_minimizer_clusters_device", "gcsa2_kmer_clusters_batch",
+    "gcsa2_minimizer_clusters_batch",
     "gcsa2_host_view_save", "gcsa2_host_view_load", "gcsa2_host_view_get", "gcsa2_host_view_free",
     "gcsa2_index_create_from_file", "gcsa2_host_view_load_gcsa", "gcsa2_index_create_from_gcsa",
     "gcsa2_host_view_parse_gcsa", "gcsa2_host_view_parse_lcp", "gcsa2_host_view_serialize_gcsa", "gcsa2_host_view_serialize_lcp",
@@ -204,6 +211,11 @@ def load_library():
     L.gcsa2_kmer_top_classes_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp, vp]
     L.gcsa2_kmer_top_classes_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp]
     L.gcsa2_seed_top_classes_device.argtypes = [vp, vp, u64, vp, u64, vp, u64, u64, C.c_int, vp, u64, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_seed_clusters_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, u64, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_kmer_clusters_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, C.c_int, u64, vp, u64, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_minimizer_clusters_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, u64, vp, u64, u64, u64, vp, vp, vp, vp]
+    L.gcsa2_kmer_clusters_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, C.c_int, u64, vp, u64, u64, u64, vp, vp, vp]
+    L.gcsa2_minimizer_clusters_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, u64, vp, u64, u64, u64, vp, vp, vp]
     L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -968,6 +980,72 @@ class GCSA:
         if rc != 0:
             raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
         return dict(zip(CLASS_STATS, (int(x) for x in stats))) if want_stats else None
+
+    def _clusters_done(self, rc, stats, want_stats):
+        if rc != 0:
+            raise Gcsa2Error(rc, self._L.gcsa2_last_error().decode(errors="replace"))
+        return dict(zip(CLUSTER_STATS, (int(x) for x in stats))) if want_stats else None
+
+    def seed_clusters_device(self, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, shift, d_coord_of_bin, n_bins,
+                             band, top_n, d_top, d_summaries, stream=0, want_stats=True):
+        """gcsa2_seed_clusters_device on caller-owned device buffers (raw pointers): a seed CSR with its hit offsets and hits as any
+        hits call emits them, d_coord_of_bin n_bins u64, d_top n_groups x top_n records of eight u64 (CLUSTER) and d_summaries
+        n_groups records of three u64 (CLUSTER_SUMMARY), both written (0 / None: not wanted).  Complete on return.  Returns the
+        stats as a dict of CLUSTER_STATS, or None with want_stats=False (a NULL stats pointer)."""
+        stats = (C.c_uint64 * len(CLUSTER_STATS))() if want_stats else None
+        rc = self._L.gcsa2_seed_clusters_device(self._h, d_group_offsets or None, int(n_groups), d_seeds or None, int(n_seeds), d_hit_offsets or None,
+                                                d_hits or None, int(n_hits), int(shift), d_coord_of_bin or None, int(n_bins), int(band), int(top_n),
+                                                d_top or None, d_summaries or None, stats, stream)
+        return self._clusters_done(rc, stats, want_stats)
+
+    def kmer_clusters_device(self, d_patterns, d_offsets, n_patterns, k, stride, hit_max, sample, shift, d_coord_of_bin, n_bins, band, top_n,
+                             d_top, d_summaries, stream=0, want_stats=True):
+        """gcsa2_kmer_clusters_device: kmer_hits_device and seed_clusters_device in one call, the hits staying on the device."""
+        stats = (C.c_uint64 * len(CLUSTER_STATS))() if want_stats else None
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        rc = self._L.gcsa2_kmer_clusters_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(stride), int(hit_max), over,
+                                                int(shift), d_coord_of_bin or None, int(n_bins), int(band), int(top_n), d_top or None, d_summaries or None,
+                                                stats, stream)
+        return self._clusters_done(rc, stats, want_stats)
+
+    def minimizer_clusters_device(self, d_patterns, d_offsets, n_patterns, k, w, hash_seed, hit_max, sample, shift, d_coord_of_bin, n_bins, band,
+                                  top_n, d_top, d_summaries, stream=0, want_stats=True):
+        """gcsa2_minimizer_clusters_device: minimizer_hits_device and seed_clusters_device in one call."""
+        stats = (C.c_uint64 * len(CLUSTER_STATS))() if want_stats else None
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        rc = self._L.gcsa2_minimizer_clusters_device(self._h, d_patterns, d_offsets, n_patterns, int(k), int(w), int(hash_seed), int(hit_max), over,
+                                                     int(shift), d_coord_of_bin or None, int(n_bins), int(band), int(top_n), d_top or None,
+                                                     d_summaries or None, stats, stream)
+        return self._clusters_done(rc, stats, want_stats)
+
+    def _clusters_batch(self, call, patterns, offsets, head, hit_max, sample, shift, coord_of_bin, band, top_n, top, summaries):
+        patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        coord_of_bin = np.ascontiguousarray(coord_of_bin, dtype=np.uint64)
+        n = max(offsets.shape[0], 1) - 1
+        out_top = np.zeros((n, max(int(top_n), 0), len(CLUSTER)), dtype=np.uint64) if top else None
+        out_sums = np.zeros((n, len(CLUSTER_SUMMARY)), dtype=np.uint64) if summaries else None
+        stats = (C.c_uint64 * len(CLUSTER_STATS))()
+        over = sample if isinstance(sample, int) and not isinstance(sample, bool) else (1 if sample else 0)
+        _check(call(self._h, _p8(patterns), _p64(offsets), n, *head, int(hit_max), over, int(shift),
+                    coord_of_bin.ctypes.data if coord_of_bin.shape[0] else None, coord_of_bin.shape[0], int(band), int(top_n),
+                    out_top.ctypes.data if top else None, out_sums.ctypes.data if summaries else None, stats))
+        return out_top, out_sums, dict(zip(CLUSTER_STATS, (int(x) for x in stats)))
+
+    def kmer_clusters_batch(self, patterns, offsets, k, coord_of_bin, top_n, stride=1, hit_max=0, sample=False, shift=10, band=0, top=True,
+                            summaries=True):
+        """Per read, the top_n diagonal bands of the hits of its k-mers (gcsa2_kmer_clusters_batch): (top, summaries, stats).  top:
+        (reads, top_n, 8) uint64 with the columns CLUSTER, larger covered first, all zero behind the last cluster; summaries:
+        (reads, 3) uint64 with the columns CLUSTER_SUMMARY; either is None when not asked for.  stats: a dict of CLUSTER_STATS.
+        coord_of_bin: uint64 coordinates of the bins value >> shift, UNKNOWN for a bin without one."""
+        return self._clusters_batch(self._L.gcsa2_kmer_clusters_batch, patterns, offsets, (int(k), int(stride)), hit_max, sample, shift, coord_of_bin,
+                                    band, top_n, top, summaries)
+
+    def minimizer_clusters_batch(self, patterns, offsets, k, w, coord_of_bin, top_n, hash_seed=0, hit_max=0, sample=False, shift=10, band=0,
+                                 top=True, summaries=True):
+        """The same over the (w, k)-minimizers of every read (gcsa2_minimizer_clusters_batch)."""
+        return self._clusters_batch(self._L.gcsa2_minimizer_clusters_batch, patterns, offsets, (int(k), int(w), int(hash_seed)), hit_max, sample,
+                                    shift, coord_of_bin, band, top_n, top, summaries)
 
     def lf_node_batch(self, nodes):
         nodes = np.ascontiguousarray(nodes, dtype=np.uint64)

@@ -23,6 +23,7 @@
 //                                                                        include/gcsa/gcsa.h:155-162, src/gcsa.cpp:802-809
 //   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
 //   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
+//   kernels_clusters.hpp k_clusters_*         per read the top diagonal bands of its seed hits (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
 //   kernels_kmers.hpp   k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //                       k_kmer_compare        compareKMers               src/algorithms.cpp:505-616
@@ -67,6 +68,7 @@ using namespace g2;
 #include "kernels_seeds.hpp"
 #include "kernels_support.hpp"
 #include "kernels_classes.hpp"
+#include "kernels_clusters.hpp"
 #include "kernels_kmers.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
@@ -6355,6 +6357,340 @@ int gcsa2_seed_top_classes_device(const gcsa2_index* ix, const uint64_t* d_group
 {
   const ClassesJob job{hit_max, shift, flags, d_class_of_bin, n_bins, n_classes, nullptr, nullptr, top_n, d_top, d_summaries};
   return seed_classes_entry(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_weights, job, true, "seed_top_classes", stats, stream);
+}
+
+}  // extern "C"
+
+// ==== seed clusters: per read (or group of seed records) the top diagonal bands of its anchors (kernels_clusters.hpp) ====
+namespace {
+
+// what a clusters call places with and writes
+struct ClustersJob
+{
+  u64 shift; const u64* coord_of_bin; u64 n_bins, band, top_n;
+  gcsa2_cluster* top; gcsa2_cluster_summary* summaries;
+};
+
+// what every form refuses before any device is touched
+int clusters_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, u64 n_bins, u64 top_n, const char* map_name)
+{
+  CHECK_INDEX(ix);
+  if(top_n == 0 || top_n > GCSA2_CLUSTER_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: top_n must be 1 .. GCSA2_CLUSTER_TOP_LIMIT (64)"); }
+  if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: shift must be below 64"); }
+  if(n_bins == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: n_bins must be at least 1"); }
+  if(coord_of_bin == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string("clusters: ") + map_name + " is NULL"); }
+  return GCSA2_OK;
+}
+
+// GCSA2_CLUSTER_LDS (a test knob, read per call): the anchors of a group that k_clusters_lds holds, a power of two from
+// CLU_CAP_MIN to CLU_CAP_DEFAULT; anything else is ignored.  No result but stats.spilled depends on it.
+u32 cluster_capacity()
+{
+  const char* env = std::getenv("GCSA2_CLUSTER_LDS");
+  if(env != nullptr && *env != 0)
+  {
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(env, &end, 10);
+    if(end != env && *end == 0 && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
+  }
+  return CLU_CAP_DEFAULT;
+}
+
+// The cluster core.  n_groups >= 1; n_groups, n_seeds, n_hits < 2^32.  Writes every row and summary and fills every field of
+// *out but `groups`.  One host round trip (the plan's counters: the largest group in LDS sizes the launch, the anchors above
+// the capacity size the large path), then the end.  Scratch: 16 bytes per group; for the large path 8 bytes per group and 92
+// bytes per anchor of a group above the capacity, and hipCUB's.
+int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa2_mem* seeds, u64 n_seeds, const u64* hoff, const u64* hits, u64 n_hits,
+                  const ClustersJob& job, gcsa2_cluster_stats* out, Scratch& scratch, hipStream_t st)
+{
+  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  const u64* recs = reinterpret_cast<const u64*>(seeds);
+  const CluMap map{u32(job.shift), job.coord_of_bin, job.n_bins};
+  const u32 cap = cluster_capacity(), top_n = u32(job.top_n);
+  unsigned long long* stat = nullptr;
+  u64 *info = nullptr, *lsize = nullptr;
+  HIP_TRY(scratch.get(stat, CLU_WORDS));
+  HIP_TRY(scratch.get(info, n_groups));
+  HIP_TRY(scratch.get(lsize, n_groups + 1));
+  HIP_TRY(hipMemsetAsync(stat, 0, CLU_WORDS * sizeof(unsigned long long), st));
+  scratch.settled = false;
+  const u64 resident = u64(ix->compute_units) * 8;
+  hipLaunchKernelGGL(k_clusters_plan, dim3(unsigned(std::min<u64>((n_groups + 3) / 4, resident))), dim3(TPB), 0, st, goff, n_groups, n_seeds, hoff, n_hits,
+                     u64(cap), info, lsize, stat);
+  LAUNCH_CHECK("k_clusters_plan");
+  unsigned long long host_stat[CLU_WORDS];
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // the groups in LDS: one wavefront each up to CLU_WAVE_MAX anchors, a workgroup of 256 lanes each above; a launch takes the
+  // LDS of its largest group
+  {
+    const u64 most = host_stat[CLU_MAX_SMALL];
+    if(most > cap) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: a group in LDS above the capacity"); }
+    u32 fit = CLU_CAP_MIN;
+    while(fit < most && fit < CLU_WAVE_MAX) { fit *= 2; }
+    const u64 narrow = std::min<u64>(fit, cap);                 // the groups of up to this many anchors
+    size_t lds = size_t(fit) * CLU_LDS_BYTES;
+    u64 per_cu = std::max<u64>(1, std::min<u64>(32, (160u << 10) / (lds + 2048)));
+    hipLaunchKernelGGL((k_clusters_lds<64>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(64), lds, st, goff, n_groups,
+                       recs, hoff, hits, info, map, job.band, top_n, fit, u64(0), narrow, job.top, job.summaries, stat);
+    LAUNCH_CHECK("k_clusters_lds");
+    if(most > narrow)
+    {
+      while(fit < most) { fit *= 2; }
+      lds = size_t(fit) * CLU_LDS_BYTES;
+      if(lds > (48u << 10))
+      {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_clusters_lds<TPB>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+      }
+      per_cu = std::max<u64>(1, std::min<u64>(8, (160u << 10) / (lds + 2048)));
+      hipLaunchKernelGGL((k_clusters_lds<TPB>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(TPB), lds, st, goff, n_groups,
+                         recs, hoff, hits, info, map, job.band, top_n, fit, narrow, u64(cap), job.top, job.summaries, stat);
+      LAUNCH_CHECK("k_clusters_lds");
+    }
+  }
+  // the groups above the capacity
+  const u64 count = host_stat[CLU_LARGE];
+  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: more anchors than hits"); }
+  if(count > 0)
+  {
+    u64 *loff = nullptr, *dk = nullptr, *pe = nullptr, *gk = nullptr, *ka = nullptr, *kb = nullptr, *sdk = nullptr, *spe = nullptr, *sgk = nullptr;
+    u64 *key2 = nullptr, *ends = nullptr, *reach = nullptr;
+    u32 *pa = nullptr, *pb = nullptr;
+    char* tmp = nullptr;
+    HIP_TRY(scratch.get(loff, n_groups + 1));
+    HIP_TRY(scratch.get(dk, count)); HIP_TRY(scratch.get(pe, count)); HIP_TRY(scratch.get(gk, count));
+    HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
+    HIP_TRY(scratch.get(sdk, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
+    HIP_TRY(scratch.get(key2, count)); HIP_TRY(scratch.get(ends, count)); HIP_TRY(scratch.get(reach, count));
+    HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count));
+    size_t bytes = 0, need = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, lsize, loff, size_t(n_groups + 1), st)); bytes = std::max(bytes, need);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, ka, pa, pb, size_t(count), 0, 64, st)); bytes = std::max(bytes, need);
+    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, ka, kb, hipcub::Max(), size_t(count), st)); bytes = std::max(bytes, need);
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, ka, kb, size_t(count), st)); bytes = std::max(bytes, need);
+    HIP_TRY(scratch.get(tmp, bytes));
+    const dim3 lanes(grid_for(count));
+    HIP_TRY(hipMemsetAsync(lsize + n_groups, 0, sizeof(u64), st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, lsize, loff, size_t(n_groups + 1), st));
+    hipLaunchKernelGGL(k_clusters_large_gather, lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, dk, pe, gk, pa);
+    LAUNCH_CHECK("k_clusters_large_gather");
+    // by (group, unplaced, diagonal): the diagonal first, then a stable sort by the group word
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, dk, ka, pa, pb, size_t(count), 0, 64, st));                     // pb: by diagonal
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, gk, pb, count, ka);
+    LAUNCH_CHECK("k_clusters_large_take");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, sgk, pb, pa, size_t(count), 0, 34, st));                    // sgk, pa: by (group, diagonal)
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, dk, pa, count, sdk);
+    LAUNCH_CHECK("k_clusters_large_take");
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, pe, pa, count, spe);
+    LAUNCH_CHECK("k_clusters_large_take");
+    // the cluster of every anchor, then (cluster, position) order
+    hipLaunchKernelGGL(k_clusters_large_heads, lanes, dim3(TPB), 0, st, sdk, sgk, count, job.band, ka);
+    LAUNCH_CHECK("k_clusters_large_heads");
+    HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, bytes, ka, kb, hipcub::Max(), size_t(count), st));                       // kb: the head of every anchor
+    hipLaunchKernelGGL(k_clusters_large_keys, lanes, dim3(TPB), 0, st, kb, spe, sgk, count, ka, pa);
+    LAUNCH_CHECK("k_clusters_large_keys");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, key2, pa, pb, size_t(count), 0, 64, st));
+    // the running end, then covered and starts as one wrapping sum
+    hipLaunchKernelGGL(k_clusters_large_ends, lanes, dim3(TPB), 0, st, key2, pb, spe, sgk, count, ends);
+    LAUNCH_CHECK("k_clusters_large_ends");
+    HIP_TRY(hipcub::DeviceScan::InclusiveScan(tmp, bytes, ends, reach, hipcub::Max(), size_t(count), st));
+    hipLaunchKernelGGL(k_clusters_large_cover, lanes, dim3(TPB), 0, st, key2, ends, reach, sgk, count, ka);
+    LAUNCH_CHECK("k_clusters_large_cover");
+    HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, bytes, ka, kb, size_t(count), st));
+    const dim3 grid(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * 8)));
+    hipLaunchKernelGGL(k_clusters_large_score, grid, dim3(TPB), 0, st, loff, lsize, n_groups, sdk, spe, sgk, key2, kb, top_n, job.top, job.summaries, stat);
+    LAUNCH_CHECK("k_clusters_large_score");
+  }
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  out->invalid_groups = host_stat[CLU_INVALID]; out->seeds = host_stat[CLU_SEEDS]; out->anchors = host_stat[CLU_ANCHORS];
+  out->unplaced = host_stat[CLU_UNPLACED]; out->clusters = host_stat[CLU_CLUSTERS]; out->spilled = host_stat[CLU_SPILLED];
+  return GCSA2_OK;
+}
+
+// The fused forms after their argument checks (0 < n_patterns < 2^32): the windows (every stride-th, or the minimizers), the
+// hits call's own core behind them (kmer_hits_found) into scratch of this call, then the cluster core with the seed offsets
+// as the groups.  The hit buffer is sized by a guess -- four hits per window, no more than hit_max allows -- and a batch
+// beyond it runs the hits again with the size the first run reported.
+int fused_clusters_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
+                        u64 w, u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, gcsa2_cluster_stats* out, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *woff = nullptr, total = 0;
+  gcsa2_minimizer* mins = nullptr;
+  int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, "minimizer_clusters", st,
+                                          woff, mins, total)
+                       : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_clusters", st, woff, total));
+  if(rc != GCSA2_OK) { return rc; }
+  u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0;
+  gcsa2_mem* seeds = nullptr;
+  u64 room = std::max<u64>(4 * total, 1024);
+  if(hit_max > 0 && hit_max < 4) { room = std::max<u64>(hit_max * total, 1); }
+  HIP_TRY(scratch.get(seed_off, n_patterns + 1));
+  HIP_TRY(scratch.get(seeds, total));
+  HIP_TRY(scratch.get(hit_off, total + 1));
+  HIP_TRY(scratch.get(hit_values, room));
+  rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
+                       total, &m, hit_off, hit_values, room, &h, st);
+  if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && m <= total && h > room)
+  {
+    room = h;
+    HIP_TRY(scratch.get(hit_values, room));
+    g_error.clear();
+    rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
+                         total, &m, hit_off, hit_values, room, &h, st);
+  }
+  if(rc != GCSA2_OK) { return rc; }
+  if(m >= (u64(1) << 32) || h >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "clusters: 2^32 or more seeds or hits in one call; split the batch"); }
+  return clusters_core(ix, seed_off, n_patterns, seeds, m, hit_off, hit_values, h, job, out, scratch, st);
+}
+
+int fused_clusters_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
+                         u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, const char* name, gcsa2_cluster_stats* stats, void* stream)
+{
+  u64 unused_seeds = 0, unused_hits = 0;
+  int rc = clusters_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.top_n, "d_coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
+  gcsa2_cluster_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.groups = n_patterns;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  rc = fused_clusters_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+}
+
+// Both host forms.  The coordinate map goes to the device once; each piece (for_read_pieces) is one fused device call on its
+// thread's stream into device rows and summaries of its own, copied to the piece's place in the caller's arrays.
+int clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
+                   u64 hash_seed, u64 hit_max, int over, u64 shift, const uint64_t* coord_of_bin, u64 n_bins, u64 band, u64 top_n, gcsa2_cluster* top,
+                   gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats, const char* name)
+{
+  u64 unused_seeds = 0, unused_hits = 0;
+  int rc = clusters_checks(ix, shift, coord_of_bin, n_bins, top_n, "coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
+  gcsa2_cluster_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": offsets is NULL"); }
+  rc = reads_ok(patterns, offsets, n_patterns, name);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  if(host_windows(offsets, n_patterns, k, (minimizers ? 1 : stride)) >= (u64(1) << 32))
+  {
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch");
+  }
+  DeviceGuard guard(ix->device);
+  DBuf<u64> d_map;
+  HIP_TRY(d_map.alloc(n_bins));
+  HIP_TRY(hipMemcpy(d_map.p, coord_of_bin, n_bins * sizeof(u64), hipMemcpyHostToDevice));
+  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  std::vector<gcsa2_cluster_stats> done(cut.size() - 1);
+  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
+  {
+    DBuf<u8> d_pat; DBuf<u64> d_off; DBuf<gcsa2_cluster> d_top; DBuf<gcsa2_cluster_summary> d_sum;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    hipError_t e = (top != nullptr ? d_top.alloc(p.count * top_n) : hipSuccess);
+    if(e == hipSuccess && summaries != nullptr) { e = d_sum.alloc(p.count); }
+    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+    const int piece_rc = (minimizers ? gcsa2_minimizer_clusters_device(ix, d_pat.p, d_off.p, p.count, k, w, hash_seed, hit_max, over, shift, d_map.p, n_bins, band, top_n,
+                                                                        d_top.p, d_sum.p, &done[p.c], p.stream)
+                                     : gcsa2_kmer_clusters_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, over, shift, d_map.p, n_bins, band, top_n,
+                                                                   d_top.p, d_sum.p, &done[p.c], p.stream));
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    if(top != nullptr) { e = hipMemcpy(top + p.b * top_n, d_top.p, p.count * top_n * sizeof(gcsa2_cluster), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && summaries != nullptr) { e = hipMemcpy(summaries + p.b, d_sum.p, p.count * sizeof(gcsa2_cluster_summary), hipMemcpyDeviceToHost); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    return true;
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  for(const gcsa2_cluster_stats& s : done)
+  {
+    sums.groups += s.groups; sums.invalid_groups += s.invalid_groups; sums.seeds += s.seeds; sums.anchors += s.anchors; sums.unplaced += s.unplaced;
+    sums.clusters += s.clusters; sums.spilled += s.spilled;
+  }
+  if(stats != nullptr) { *stats = sums; }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_seed_clusters_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                               const uint64_t* d_hit_offsets, const uint64_t* d_hits, uint64_t n_hits, uint64_t shift, const uint64_t* d_coord_of_bin,
+                               uint64_t n_bins, uint64_t band, uint64_t top_n, gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries,
+                               gcsa2_cluster_stats* stats, void* stream)
+{
+  int rc = clusters_checks(ix, shift, d_coord_of_bin, n_bins, top_n, "d_coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_seeds is NULL"); }
+  if(n_seeds > 0 && d_hit_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_hit_offsets is NULL"); }
+  if(n_hits > 0 && d_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_hits is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more seeds in one call; split the batch"); }
+  if(n_hits >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more hits in one call; split the batch"); }
+  gcsa2_cluster_stats sums{};
+  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  sums.groups = n_groups;
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  {
+    Scratch scratch(ix, st);
+    const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
+    rc = clusters_core(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, job, &sums, scratch, st);
+  }
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_clusters_device: ") + e.what()); }
+}
+
+int gcsa2_kmer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
+                               uint64_t hit_max, int over, uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                               gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats, void* stream)
+{
+  const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
+  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, job, "kmer_clusters", stats, stream);
+}
+
+int gcsa2_minimizer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                    uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins,
+                                    uint64_t band, uint64_t top_n, gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats,
+                                    void* stream)
+{
+  const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
+  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, job, "minimizer_clusters", stats, stream);
+}
+
+int gcsa2_kmer_clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
+                              uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                              gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats)
+{
+  return clusters_batch(ix, patterns, offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, shift, coord_of_bin, n_bins, band, top_n, top, summaries, stats,
+                        "gcsa2_kmer_clusters_batch");
+}
+
+int gcsa2_minimizer_clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                   uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band,
+                                   uint64_t top_n, gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats)
+{
+  return clusters_batch(ix, patterns, offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, shift, coord_of_bin, n_bins, band, top_n, top, summaries, stats,
+                        "gcsa2_minimizer_clusters_batch");
 }
 
 }  // extern "C"

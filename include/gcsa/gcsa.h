@@ -485,6 +485,58 @@ public:
     check(rc, "GCSA::kmer_top_classes_batch()");
   }
 
+  // Seed clusters (gcsa2_kmer_clusters_batch): per read the top_n (1 .. GCSA2_CLUSTER_TOP_LIMIT) diagonal bands of the hits of
+  // its k-mers -- larger covered first, then more anchors, then the smaller diag_min; all zero behind the last cluster -- and
+  // {anchors, unplaced, clusters}.  coord_of_bin[value >> shift] is the coordinate of a hit (GCSA2_UNKNOWN: none); anchors whose
+  // diagonals differ by at most `band` join.  top (reads x top_n, row-major) and summaries (one per read) are resized and
+  // WRITTEN.  Needs no LCP array.
+  void kmer_clusters_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type stride,
+                           size_type hit_max, bool sample, size_type shift, const std::vector<size_type>& coord_of_bin, size_type band,
+                           size_type top_n, std::vector<gcsa2_cluster>& top, std::vector<gcsa2_cluster_summary>& summaries,
+                           gcsa2_cluster_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    top.assign(np * (top_n <= GCSA2_CLUSTER_TOP_LIMIT ? top_n : 0), gcsa2_cluster{0, 0, 0, 0, 0, 0, 0, 0});
+    summaries.assign(np, gcsa2_cluster_summary{0, 0, 0});
+    const int rc = gcsa2_kmer_clusters_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                             k, stride, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, shift,
+                                             coord_of_bin.empty() ? nullptr : coord_of_bin.data(), coord_of_bin.size(), band, top_n,
+                                             top.empty() ? nullptr : top.data(), summaries.empty() ? nullptr : summaries.data(), stats);
+    check(rc, "GCSA::kmer_clusters_batch()");
+  }
+
+  // The same over the (w, k)-minimizers of every read (gcsa2_minimizer_clusters_batch).
+  void minimizer_clusters_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                                size_type hash_seed, size_type hit_max, bool sample, size_type shift, const std::vector<size_type>& coord_of_bin,
+                                size_type band, size_type top_n, std::vector<gcsa2_cluster>& top, std::vector<gcsa2_cluster_summary>& summaries,
+                                gcsa2_cluster_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    top.assign(np * (top_n <= GCSA2_CLUSTER_TOP_LIMIT ? top_n : 0), gcsa2_cluster{0, 0, 0, 0, 0, 0, 0, 0});
+    summaries.assign(np, gcsa2_cluster_summary{0, 0, 0});
+    const int rc = gcsa2_minimizer_clusters_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                                  k, w, hash_seed, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, shift,
+                                                  coord_of_bin.empty() ? nullptr : coord_of_bin.data(), coord_of_bin.size(), band, top_n,
+                                                  top.empty() ? nullptr : top.data(), summaries.empty() ? nullptr : summaries.data(), stats);
+    check(rc, "GCSA::minimizer_clusters_batch()");
+  }
+
+  // The clusters of a seed CSR that is already in device memory with its hit offsets and hits, as any hits call of the C
+  // interface leaves them (gcsa2_seed_clusters_device): raw device pointers, d_top and d_summaries may be null.
+  void seed_clusters_device(const size_type* d_group_offsets, size_type n_groups, const gcsa2_mem* d_seeds, size_type n_seeds,
+                            const size_type* d_hit_offsets, const node_type* d_hits, size_type n_hits, size_type shift,
+                            const size_type* d_coord_of_bin, size_type n_bins, size_type band, size_type top_n, gcsa2_cluster* d_top,
+                            gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats = nullptr, void* stream = nullptr) const
+  {
+    const int rc = gcsa2_seed_clusters_device(handle, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, shift, d_coord_of_bin,
+                                              n_bins, band, top_n, d_top, d_summaries, stats, stream);
+    check(rc, "GCSA::seed_clusters_device()");
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).

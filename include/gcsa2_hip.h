@@ -1128,6 +1128,96 @@ int gcsa2_seed_top_classes_device(const gcsa2_index* index, const uint64_t* d_gr
                                   uint64_t hit_max, uint64_t shift, int flags, const uint32_t* d_class_of_bin, uint64_t n_bins,
                                   uint64_t n_classes, uint64_t top_n, gcsa2_class_vote* d_top, gcsa2_top_summary* d_summaries,
                                   gcsa2_class_stats* stats, void* stream);
+/* ---- seed clusters: per read the top diagonal bands of its seed hits -----------------------------------------------------------
+ * Where does the read go, and do its seeds agree?  A mapper groups the hits of a read's seeds into collinear clusters by anchor
+ * diagonal (reference coordinate minus read position) before it chains or extends anything.  The hits calls above return the
+ * whole hit CSR, which has no per-read size bound; here the hits stay on the device and what leaves is, per read (or group of
+ * seed records), the top_n clusters of 64 bytes each and a summary.  The geometry is the caller's: a map from bins of located
+ * values to coordinates.
+ *
+ * DEFINITION (gcsa2_seed_clusters_device).
+ *   - Inputs: a seed CSR, hit offsets and hits exactly as every hits call emits them (gcsa2_kmer_hits_device,
+ *     gcsa2_minimizer_hits_device, gcsa2_mem_hits_device, gcsa2_sub_mem_hits_device, gcsa2_capped_seeds_device); a seed-offset
+ *     array serves as d_group_offsets (n_groups + 1 entries).  Of a seed only `position` and `length` are read.  d_hit_offsets
+ *     has n_seeds + 1 entries, d_hits n_hits.
+ *   - ANCHORS of group g: every pair (seed i of the group, hit v = d_hits[h]) with h in [d_hit_offsets[i], d_hit_offsets[i + 1]).
+ *     Anchors are a multiset: GCSA2_MEM_OVER_SAMPLE hit lists may repeat a value.
+ *   - Placement: bin = v >> shift.  The anchor is UNPLACED if bin >= n_bins, if d_coord_of_bin[bin] == GCSA2_UNKNOWN, or if
+ *     position >= 2^32, length >= 2^32 or position + length >= 2^32.  Otherwise x = d_coord_of_bin[bin] + (v & (2^shift - 1))
+ *     and diag = x - position, both in 64-bit wrapping arithmetic; diagonals are ordered as SIGNED 64-bit integers.
+ *     Node values are id << 11 | rc << 10 | offset: shift = 10 gives one coordinate per oriented node, shift = 11 one per node,
+ *     shift = 0 one per value.
+ *   - Clusters of a group: sort the placed anchors by diag; a new cluster starts wherever the unsigned difference between two
+ *     sorted neighbours exceeds `band`.  band = 0 gives exact diagonals, band = 2^64 - 1 one cluster.
+ *   - The record of a cluster: diag_min, diag_max = its extreme diagonals (signed order); anchors = the number of its anchors;
+ *     starts = the number of distinct seed positions; covered = the size of the union of [position, position + length) over its
+ *     anchors (the read bases it explains); read_begin = the smallest position; read_end = the largest position + length;
+ *     ref_begin = the unsigned minimum of x.
+ *   - The top row: order the clusters by larger covered first, then larger anchors, then smaller diag_min (signed): a total
+ *     order within a group.  d_top[g top_n + j] for j < min(top_n, clusters) is the j-th cluster; every later entry of the row
+ *     is all zero (anchors == 0 marks an empty entry).
+ *   - summary(g) = { anchors = the placed anchors, unplaced = the others, clusters = the clusters of the group }.
+ *   - Rows and summaries are WRITTEN, not added to: the call writes every entry of d_top[0 .. n_groups top_n) and of
+ *     d_summaries[0 .. n_groups), and nothing behind them.
+ *   - INVALID groups: one whose group offsets decrease or reach beyond n_seeds, or whose hit offsets over its seeds
+ *     (d_hit_offsets[first .. last]) decrease or reach beyond n_hits, is NOT READ any further -- no seed and no hit of it is
+ *     touched --; its row and summary are zero and it counts in stats.invalid_groups (the rule of gcsa2_seed_classes_device).
+ *     A group without a seed reads no hit offset and is valid.
+ *   - stats: groups = n_groups; seeds, anchors, unplaced, clusters = the sums over the valid groups; spilled = the number of
+ *     groups that took the large path (below), the only field that may depend on GCSA2_CLUSTER_LDS.
+ *   - d_top, d_summaries and stats may each be NULL; all three NULL is valid and does the work.
+ *
+ * GCSA2_ERR_INVALID_ARGUMENT, before any device is touched, with nothing written and stats untouched: a NULL index, top_n == 0
+ * or top_n > GCSA2_CLUSTER_TOP_LIMIT, shift >= 64, n_bins == 0 or a NULL map, NULL d_group_offsets with n_groups > 0, NULL
+ * d_seeds or d_hit_offsets with n_seeds > 0, NULL d_hits with n_hits > 0, and n_groups, n_seeds or n_hits >= 2^32.
+ * n_groups == 0 is GCSA2_OK with zero stats.  The call needs no component of the image (no samples, counters or LCP array).
+ * Enqueued on `stream`, complete on return.
+ *
+ * The fused forms gcsa2_kmer_clusters_device and gcsa2_minimizer_clusters_device: the hits never leave the device.  LAW: their
+ * rows, summaries and stats equal gcsa2_kmer_hits_device (gcsa2_minimizer_hits_device) with the same arguments into large
+ * enough buffers followed by gcsa2_seed_clusters_device with the seed offsets as the groups, word for word.  Refusals, limits
+ * and missing components (samples and counters) are those of the hits call plus those above.  They run the hits call's own
+ * core into scratch of the call and then the cluster core: there is no second search kernel.
+ *
+ * One workgroup owns a group of up to 4096 anchors, 32 bytes of LDS per anchor: a single wavefront for a group of up to 256
+ * anchors (8 KiB at most, so a CU holds sixteen and more of them), 256 lanes above (the launch takes what the largest group of
+ * the call needs, 128 KiB at the capacity).  It packs the placed anchors into
+ * LDS, sorts them by diagonal (bitonic), marks the cluster heads, sorts again by (cluster, position), sums covered and starts
+ * along the running end, and keeps the top row in the registers of one wavefront.  Groups above the capacity take the LARGE
+ * path -- the same steps device-wide with hipCUB radix sorts and scans, then the same scoring code over global memory --, exact
+ * for any number of anchors.  GCSA2_CLUSTER_LDS (a test knob, read per call; a power of two, 64 .. 4096, anything else is
+ * ignored) sets the capacity; no result but stats.spilled depends on it.  Global atomics serve the stats only. */
+#define GCSA2_CLUSTER_TOP_LIMIT 64               /* top_n may be 1 .. GCSA2_CLUSTER_TOP_LIMIT */
+typedef struct gcsa2_cluster { uint64_t diag_min, diag_max, anchors, starts, covered, read_begin, read_end, ref_begin; } gcsa2_cluster;
+typedef struct gcsa2_cluster_summary { uint64_t anchors, unplaced, clusters; } gcsa2_cluster_summary;
+typedef struct gcsa2_cluster_stats { uint64_t groups, invalid_groups, seeds, anchors, unplaced, clusters, spilled; } gcsa2_cluster_stats;
+int gcsa2_seed_clusters_device(const gcsa2_index* index, const uint64_t* d_group_offsets, uint64_t n_groups /* n_groups + 1 offsets */,
+                               const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                               const uint64_t* d_hit_offsets /* n_seeds + 1 */, const uint64_t* d_hits, uint64_t n_hits,
+                               uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                               gcsa2_cluster* d_top /* n_groups x top_n, row-major, or NULL */,
+                               gcsa2_cluster_summary* d_summaries /* n_groups, or NULL */,
+                               gcsa2_cluster_stats* stats /* host, or NULL */, void* stream);
+int gcsa2_kmer_clusters_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                               uint64_t k, uint64_t stride, uint64_t hit_max, int over,
+                               uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                               gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats, void* stream);
+int gcsa2_minimizer_clusters_device(const gcsa2_index* index, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns,
+                                    uint64_t k, uint64_t w, uint64_t hash_seed, uint64_t hit_max, int over,
+                                    uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                                    gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats, void* stream);
+/* The same for reads and the coordinate map in host memory, into host arrays: offsets[0] == 0, decreasing offsets are refused.
+ * A batch of two pieces' worth of read bytes or more travels in pieces of whole reads (GCSA2_MS_PIECE_MB, GCSA2_MS_THREADS);
+ * the map is uploaded once, a row belongs to one read and so does not depend on the cut, stats are summed over the pieces. */
+int gcsa2_kmer_clusters_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                              uint64_t k, uint64_t stride, uint64_t hit_max, int over,
+                              uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                              gcsa2_cluster* top /* host, n_patterns x top_n, or NULL */,
+                              gcsa2_cluster_summary* summaries /* host, or NULL */, gcsa2_cluster_stats* stats);
+int gcsa2_minimizer_clusters_batch(const gcsa2_index* index, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns,
+                                   uint64_t k, uint64_t w, uint64_t hash_seed, uint64_t hit_max, int over,
+                                   uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
+                                   gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats);
 /* Diagnostic (not the timed path): the default kernel instrumented with shader-clock counters, same results.  d_prof[16],
  * zeroed by the caller: [0..7] cycles summed over the wavefronts for the phases of a round (loop head / pattern window, step
  * setup, first block fetch, first evaluation, second fetch + evaluation, outcome + statistics, parent() from the LCP chunks,
