@@ -176,6 +176,18 @@ thread_local std::string g_error;
 
 int fail(int code, const std::string& msg) { g_error = msg; return code; }
 
+// A knob that is a count: the whole string a decimal number.  false: unset, empty or anything else (*v is then untouched).
+bool env_count(const char* name, u64* v)
+{
+  const char* env = std::getenv(name);
+  if(env == nullptr || *env == 0) { return false; }
+  char* end = nullptr;
+  const unsigned long long got = std::strtoull(env, &end, 10);
+  if(end == env || *end != 0) { return false; }
+  *v = got;
+  return true;
+}
+
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if(e_ != hipSuccess) { \
   return fail(e_ == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, \
               std::string(#expr) + ": " + hipGetErrorString(e_)); } } while(0)
@@ -5684,24 +5696,46 @@ int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, con
 
 }  // extern "C"
 
-// ==== k-mer support: read k-mers (or any seed records) summed per graph node (kernels_support.hpp) ==========================
+// ==== the calls over seed records with statistics: k-mer support, k-mer classes, seed clusters ===============================
 namespace {
 
-constexpr u64 SUPPORT_CHUNK_DEFAULT = u64(1) << 22;    // values (before deduplication) located per chunk: the smallest budget within 2.5 % of the best time, profiles/kmer_support.md
-
-// GCSA2_SUPPORT_CHUNK (a test knob, read per call): the value budget of a chunk.  The result never depends on it.
-u64 support_chunk_budget()
+// The shell of gcsa2_<name>_device after its argument checks.  `empty` (no read, no group, no record): zeroed statistics and
+// nothing else.  Otherwise core(sums) runs on the index's device, `sums` holding what the arguments alone say, and the
+// statistics reach the caller only with GCSA2_OK.
+template<class Stats, class Core>
+int stats_entry(const char* name, const gcsa2_index* ix, Stats* stats, Stats sums, bool empty, Core core)
 {
-  u64 budget = SUPPORT_CHUNK_DEFAULT;
-  const char* env = std::getenv("GCSA2_SUPPORT_CHUNK");
-  if(env != nullptr && *env != 0)
-  {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(env, &end, 10);
-    if(end != env && *end == 0 && v >= 1) { budget = v; }
-  }
-  return std::min(budget, (u64(1) << 31) - 1);       // one pass of the locate pipeline
+  if(empty) { if(stats != nullptr) { *stats = Stats{}; } return GCSA2_OK; }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  const int rc = core(sums);
+  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
+  return rc;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
 }
+
+// a += b, counter by counter, for the host forms that sum their pieces' statistics
+template<class Stats>
+void sum_stats(Stats& a, const Stats& b)
+{
+  constexpr size_t N = sizeof(Stats) / sizeof(uint64_t);
+  static_assert(sizeof(Stats) == N * sizeof(uint64_t) && std::is_trivially_copyable<Stats>::value, "a struct of uint64_t counters and nothing else");
+  uint64_t x[N], y[N];
+  std::memcpy(x, &a, sizeof(Stats)); std::memcpy(y, &b, sizeof(Stats));
+  for(size_t i = 0; i < N; i++) { x[i] += y[i]; }
+  std::memcpy(&a, x, sizeof(Stats));
+}
+static_assert(sizeof(gcsa2_support_stats) == 7 * sizeof(uint64_t) && sizeof(gcsa2_class_stats) == 8 * sizeof(uint64_t) &&
+              sizeof(gcsa2_cluster_stats) == 7 * sizeof(uint64_t), "sum_stats: a field of another type was added");
+
+}  // namespace
+
+// ==== seed records folded into runs of equal ranges and located chunk by chunk: what k-mer support and k-mer classes share ====
+#include "host_fold.hpp"
+
+// ==== k-mer support: read k-mers (or any seed records) summed per graph node (kernels_support.hpp) ==========================
+namespace {
 
 // what every form refuses before any device is touched, then the components the call needs (no LCP array)
 int support_checks(const gcsa2_index* ix, u64 shift, int flags, const void* support, u64 n_bins, const char* support_name)
@@ -5723,104 +5757,36 @@ int kmer_support_checks(const gcsa2_index* ix, u64 k, u64 stride, u64 shift, int
 
 // Steps 2 onward of a support call: m (1 <= m < 2^32) records of `words` u64 with (sp, ep) at words 2 and 3, their count()s
 // in `known` or (nullptr) computed here, weights or (nullptr) 1 each, are added to d_support.  Fills every field of *st_out
-// but `windows`.  Host round trips: the number of counted records, the number of distinct ranges, one per chunk for its cut,
-// those of every chunk's locate pass, the end.  Scratch: per counted record 50 bytes and the sorts' temporaries; per distinct
-// range 32 bytes; per chunk -- the same buffers for every chunk -- 8 bytes per range and 8 1/8 bytes per value of the largest.
+// but `windows`.  Host round trips: those of fold_seed_ranges, cut_chunks and for_located_chunks (host_fold.hpp), the end.
+// Scratch: theirs.
 int support_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* known, const u64* weights, u64 m, u64 hit_max, u64 shift, int flags,
                  u64* d_support, u64 n_bins, gcsa2_support_stats* st_out, Scratch& scratch, hipStream_t st)
 {
-  // 1. the cap first: only the counted records reach the sort
   unsigned long long* stat = nullptr;
-  u64 *csp = nullptr, *cep = nullptr, *ccnt = nullptr, *cw = nullptr;
   HIP_TRY(scratch.get(stat, SUP_WORDS));
-  HIP_TRY(scratch.get(csp, m)); HIP_TRY(scratch.get(cep, m)); HIP_TRY(scratch.get(ccnt, m));
-  if(weights != nullptr) { HIP_TRY(scratch.get(cw, m)); }
-  HIP_TRY(hipMemsetAsync(stat, 0, SUP_WORDS * sizeof(unsigned long long), st));
-  hipLaunchKernelGGL(k_support_class, dim3(unsigned((m + SUPPORT_CLASS_TPB - 1) / SUPPORT_CLASS_TPB)), dim3(SUPPORT_CLASS_TPB), 0, st, ix->img, recs, words, known, weights, m, hit_max, stat, csp, cep, ccnt, cw);
-  LAUNCH_CHECK("k_support_class");
-  unsigned long long host_stat[SUP_WORDS];
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const u64 c = host_stat[SUP_CURSOR] & 0xFFFFFFFFull;
-  st_out->found = host_stat[SUP_CURSOR] >> 32;
-  st_out->counted = c;
-  if(c == 0) { scratch.settled = true; return GCSA2_OK; }
-  // 2. equal ranges fold: stable radix passes by ep, then by sp, over as many bits as a path node has
-  u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
-  int bits = 1;
-  while(bits < 64 && (top >> bits) != 0) { bits++; }
-  u64 *key_a = nullptr, *key_b = nullptr, *ranges = nullptr, *run_counts = nullptr, *run_off = nullptr;
-  u32 *perm_a = nullptr, *perm_b = nullptr, *head = nullptr, *run = nullptr;
-  unsigned long long* mult = nullptr;
-  char* tmp = nullptr;
-  HIP_TRY(scratch.get(key_a, c)); HIP_TRY(scratch.get(key_b, c));
-  HIP_TRY(scratch.get(perm_a, c)); HIP_TRY(scratch.get(perm_b, c));
-  HIP_TRY(scratch.get(head, c)); HIP_TRY(scratch.get(run, c));
-  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, head, run, size_t(c), st));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, key_a, key_b, size_t(c + 1), st));
-  HIP_TRY(scratch.get(tmp, std::max(sort_bytes, std::max(scan_bytes, sum_bytes))));
-  hipLaunchKernelGGL(k_support_iota, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, c);
-  LAUNCH_CHECK("k_support_iota");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));      // perm_b: by ep
-  hipLaunchKernelGGL(k_support_gather, dim3(grid_for(c)), dim3(TPB), 0, st, csp, perm_b, c, key_a);
-  LAUNCH_CHECK("k_support_gather");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, perm_b, perm_a, size_t(c), 0, bits, st));    // key_b, perm_a: by (sp, ep)
-  hipLaunchKernelGGL(k_support_heads, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, perm_a, c, head);
-  LAUNCH_CHECK("k_support_heads");
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, scan_bytes, head, run, size_t(c), st));
-  u32 d32 = 0;
-  HIP_TRY(hipMemcpyAsync(&d32, run + (c - 1), sizeof(u32), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const u64 d = d32;
-  st_out->distinct = d;
-  HIP_TRY(scratch.get(ranges, 2 * d)); HIP_TRY(scratch.get(run_counts, d + 1)); HIP_TRY(scratch.get(run_off, d + 1)); HIP_TRY(scratch.get(mult, d));
-  HIP_TRY(hipMemsetAsync(mult, 0, d * sizeof(unsigned long long), st));
-  HIP_TRY(hipMemsetAsync(run_counts + d, 0, sizeof(u64), st));
-  hipLaunchKernelGGL(k_support_runs, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, ccnt, cw, perm_a, run, c, ranges, run_counts, mult);
-  LAUNCH_CHECK("k_support_runs");
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, sum_bytes, run_counts, run_off, size_t(d + 1), st));
-  // 3. the chunks: runs q0 .. q1 - 1 whose count() sum stays within the budget, one run at least
-  const u64 budget = support_chunk_budget();
-  struct Chunk { u64 q0, q1, raw; };
-  std::vector<Chunk> chunks;
-  unsigned long long* d_cut = stat + SUP_CUT;
-  u64 most_runs = 0, most_raw = 0;
-  for(u64 q0 = 0; q0 < d; )
-  {
-    unsigned long long cut[2] = {0, 0};
-    hipLaunchKernelGGL(k_support_cut, dim3(1), dim3(1), 0, st, run_off, d, q0, budget, ix->tune.locate_split_queries, d_cut);
-    LAUNCH_CHECK("k_support_cut");
-    HIP_TRY(hipMemcpyAsync(cut, d_cut, sizeof(cut), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const u64 q1 = cut[0], raw = cut[1];
-    if(q1 <= q0 || q1 > d) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "support: a chunk without a range"); }
-    chunks.push_back(Chunk{q0, q1, raw});
-    most_runs = std::max(most_runs, q1 - q0); most_raw = std::max(most_raw, raw);
-    q0 = q1;
-  }
-  // 4. locate and add, chunk by chunk, in the same scratch
-  u64 *off = nullptr, *val = nullptr, *owners = nullptr;
-  HIP_TRY(scratch.get(off, most_runs + 1)); HIP_TRY(scratch.get(val, most_raw)); HIP_TRY(scratch.get(owners, most_raw / OWNER_SPAN + 3));
+  SeedFold fold;
+  int rc = fold_seed_ranges(ix, recs, words, known, weights, m, hit_max, false, stat, fold, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  st_out->found = fold.found;
+  st_out->counted = fold.counted;
+  if(fold.counted == 0) { scratch.settled = true; return GCSA2_OK; }
+  st_out->distinct = fold.distinct;
+  SeedChunks chunks;
+  rc = cut_chunks(ix, fold, stat + SUP_CUT, "support", chunks, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  // locate and add, chunk by chunk
   u64 values = 0;
-  for(const Chunk& chunk : chunks)
+  rc = for_located_chunks(ix, fold, chunks, "support", &values, scratch, st, []() -> int { return GCSA2_OK; },
+                          [&](const SeedChunk& chunk, u64 runs, u64 total, const u64* off, const u64* val, const u64* owners, u64) -> int
   {
-    const u64 runs = chunk.q1 - chunk.q0;
-    u64 total = 0;
-    ValuesProvider provide = [val, most_raw](u64 count) -> u64* { return count <= most_raw ? val : nullptr; };
-    const int rc = locate_core(ix, ranges + 2 * chunk.q0, runs, 1, off, provide, &total, st, val, most_raw);
-    if(rc != GCSA2_OK) { return rc; }
-    values += total;
-    if(total == 0) { continue; }
-    const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
-    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, off, runs, total, OWNER_SPAN, spans, owners);
-    LAUNCH_CHECK("k_block_owners");
-    hipLaunchKernelGGL(k_support_add, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, runs, total, mult + chunk.q0, u32(shift),
+    hipLaunchKernelGGL(k_support_add, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, runs, total, fold.mult + chunk.q0, u32(shift),
                        int((flags & GCSA2_SUPPORT_PER_BIN) != 0), reinterpret_cast<unsigned long long*>(d_support), n_bins, stat);
     LAUNCH_CHECK("k_support_add");
     scratch.settled = false;
-  }
+    return GCSA2_OK;
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  unsigned long long host_stat[SUP_WORDS];
   HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   scratch.settled = true;
@@ -5864,15 +5830,10 @@ int gcsa2_kmer_support_device(const gcsa2_index* ix, const uint8_t* d_patterns, 
   if(rc != GCSA2_OK) { return rc; }
   if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "kmer_support: d_offsets is NULL"); }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "kmer_support: 2^32 or more reads in one call; split the batch"); }
-  gcsa2_support_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  rc = kmer_support_core(ix, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_support, n_bins, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_kmer_support_device: ") + e.what()); }
+  return stats_entry("kmer_support", ix, stats, gcsa2_support_stats{}, n_patterns == 0, [&](gcsa2_support_stats& sums) -> int
+  {
+    return kmer_support_core(ix, d_patterns, d_offsets, n_patterns, k, stride, hit_max, shift, flags, d_support, n_bins, &sums, static_cast<hipStream_t>(stream));
+  });
 }
 
 int gcsa2_seed_support_device(const gcsa2_index* ix, const gcsa2_mem* d_seeds, uint64_t n_seeds, const uint64_t* d_weights, uint64_t hit_max,
@@ -5882,21 +5843,15 @@ int gcsa2_seed_support_device(const gcsa2_index* ix, const gcsa2_mem* d_seeds, u
   if(rc != GCSA2_OK) { return rc; }
   if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_support: d_seeds is NULL"); }
   if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "seed_support: 2^32 or more seeds in one call; split the batch"); }
-  gcsa2_support_stats sums{};
-  sums.windows = n_seeds;
-  if(n_seeds == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  gcsa2_support_stats pre{};
+  pre.windows = n_seeds;
+  return stats_entry("seed_support", ix, stats, pre, n_seeds == 0, [&](gcsa2_support_stats& sums) -> int
   {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
     Scratch scratch(ix, st);
-    rc = support_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, hit_max, shift, flags, d_support, n_bins, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_support_device: ") + e.what()); }
+    return support_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, hit_max, shift, flags, d_support, n_bins, &sums, scratch, st);
+  });
 }
 
 // The host form.  One zeroed device array of n_bins for the whole call; each piece (for_read_pieces) is one
@@ -5932,11 +5887,7 @@ int gcsa2_kmer_support_batch(const gcsa2_index* ix, const uint8_t* patterns, con
     return true;
   });
   if(rc != GCSA2_OK) { return rc; }
-  for(const gcsa2_support_stats& s : done)
-  {
-    sums.windows += s.windows; sums.found += s.found; sums.counted += s.counted; sums.distinct += s.distinct;
-    sums.values += s.values; sums.added += s.added; sums.dropped += s.dropped;
-  }
+  for(const gcsa2_support_stats& s : done) { sum_stats(sums, s); }
   if(n_bins > 0)
   {
     std::vector<u64> got(n_bins);
@@ -5999,14 +5950,8 @@ struct ClassesJob
 // TOP_SLOTS_MIN and TOP_SLOTS_MAX.  The result never depends on it.
 u32 top_slots()
 {
-  u64 slots = TOP_SLOTS_DEFAULT;
-  const char* env = std::getenv("GCSA2_TOP_SLOTS");
-  if(env != nullptr && *env != 0)
-  {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(env, &end, 10);
-    if(end != env && *end == 0) { slots = std::min<u64>(std::max<u64>(v, TOP_SLOTS_MIN), TOP_SLOTS_MAX); }
-  }
+  u64 slots = TOP_SLOTS_DEFAULT, v = 0;
+  if(env_count("GCSA2_TOP_SLOTS", &v)) { slots = std::min<u64>(std::max<u64>(v, TOP_SLOTS_MIN), TOP_SLOTS_MAX); }
   u32 out = TOP_SLOTS_MIN;
   while(u64(out) * 2 <= slots) { out *= 2; }
   return out;
@@ -6016,21 +5961,24 @@ u32 top_slots()
 // `known` or (nullptr) computed here, weights or (nullptr) 1 each.  n_groups (1 <= n_groups < 2^32) groups: with `windows`,
 // group q owns the windows [group_off[q], group_off[q + 1]) of a search of `limit` windows whose wavefronts left wave_base /
 // wave_mask; otherwise the records [group_off[q], group_off[q + 1]), limit = m.  Writes every row and call and fills every
-// field of *st_out but `windows`.  Host round trips: those of support_tail.  Scratch: per record 28 bytes; per counted record
-// 36 bytes and the sorts' temporaries; per distinct range 56 bytes; per value that the distinct ranges count() 8 bytes (the
-// signatures, which stay); per chunk -- the same buffers for every chunk -- 8 bytes per range and 28 1/8 bytes per value of
-// the largest, and hipCUB's.  A range of 2^31 or more values is refused (one run-length encoding per chunk).
+// field of *st_out but `windows`.  Host round trips: those of support_tail.  Scratch: that of fold_seed_ranges with slots,
+// cut_chunks and for_located_chunks (host_fold.hpp); per value that the distinct ranges count() 8 bytes (the signatures, which
+// stay); per chunk -- the same buffers for every chunk -- 20 bytes per value of the largest, and hipCUB's.  A range of 2^31 or
+// more values is refused (one run-length encoding per chunk).
 int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* known, const u64* weights, u64 m, bool windows, const u64* group_off,
                  u64 n_groups, u64 limit, const u32* wave_base, const u64* wave_mask, const ClassesJob& job, gcsa2_class_stats* st_out,
                  Scratch& scratch, hipStream_t st)
 {
   unsigned long long* stat = nullptr;
-  u32 *slot = nullptr, *run_of = nullptr;
-  u64 *span = nullptr, *sig = nullptr;
   HIP_TRY(scratch.get(stat, CLS_WORDS));
-  HIP_TRY(hipMemsetAsync(stat, 0, CLS_WORDS * sizeof(unsigned long long), st));
-  scratch.settled = false;
-  unsigned long long host_stat[CLS_WORDS];
+  // steps 1 and 2: the cap, every record keeping its compacted place, and the fold.  The runs' multiplicities are not needed.
+  SeedFold fold;
+  int rc = fold_seed_ranges(ix, recs, words, known, nullptr, m, job.hit_max, true, stat, fold, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  st_out->found = fold.found;
+  st_out->counted = fold.counted;
+  st_out->distinct = fold.distinct;
+  u64* sig = nullptr;
   // the last step, from wherever the records run out: every row and call is written, with or without a counted record
   auto vote = [&]() -> int
   {
@@ -6041,17 +5989,18 @@ int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* k
       const u32 slots = top_slots();
       const size_t lds = size_t(slots) * (sizeof(u64) + sizeof(u32));
       const dim3 fit(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * std::min<u64>(32, (160u << 10) / lds))));   // as many as a CU's LDS holds
-      if(windows) { hipLaunchKernelGGL((k_classes_top<true>), fit, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, slots, u32(job.top_n), job.top, job.summaries, stat); }
-      else { hipLaunchKernelGGL((k_classes_top<false>), fit, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, slots, u32(job.top_n), job.top, job.summaries, stat); }
+      hipLaunchKernelGGL((windows ? k_classes_top<true> : k_classes_top<false>), fit, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask,
+                         fold.slot, fold.run_of, fold.span, sig, weights, job.flags, slots, u32(job.top_n), job.top, job.summaries, stat);
       LAUNCH_CHECK("k_classes_top");
     }
     else
     {
       const size_t lds = size_t(job.n_classes) * sizeof(u64);
-      if(windows) { hipLaunchKernelGGL((k_classes_vote<true>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
-      else { hipLaunchKernelGGL((k_classes_vote<false>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask, slot, run_of, span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat); }
+      hipLaunchKernelGGL((windows ? k_classes_vote<true> : k_classes_vote<false>), grid, dim3(64), lds, st, group_off, n_groups, limit, wave_base, wave_mask,
+                         fold.slot, fold.run_of, fold.span, sig, weights, job.flags, u32(job.n_classes), job.votes, job.calls, stat);
       LAUNCH_CHECK("k_classes_vote");
     }
+    unsigned long long host_stat[CLS_WORDS];
     HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     scratch.settled = true;
@@ -6060,120 +6009,46 @@ int classes_tail(const gcsa2_index* ix, const u64* recs, u32 words, const u64* k
     st_out->ambiguous = host_stat[CLS_AMBIGUOUS];
     return GCSA2_OK;
   };
-  if(m == 0) { return vote(); }
-  // 1. the cap first: only the counted records reach the sort; every record keeps its compacted place
-  u64 *csp = nullptr, *cep = nullptr, *ccnt = nullptr;
-  HIP_TRY(scratch.get(slot, m));
-  HIP_TRY(scratch.get(csp, m)); HIP_TRY(scratch.get(cep, m)); HIP_TRY(scratch.get(ccnt, m));
-  hipLaunchKernelGGL(k_classes_fold, dim3(unsigned((m + CLASSES_FOLD_TPB - 1) / CLASSES_FOLD_TPB)), dim3(CLASSES_FOLD_TPB), 0, st, ix->img, recs, words, known, m, job.hit_max, stat, csp, cep, ccnt, slot);
-  LAUNCH_CHECK("k_classes_fold");
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const u64 c = host_stat[CLS_CURSOR] & 0xFFFFFFFFull;
-  st_out->found = host_stat[CLS_CURSOR] >> 32;
-  st_out->counted = c;
-  if(c == 0) { return vote(); }
-  // 2. equal ranges fold, as support_tail does; the runs' multiplicities are not needed, their numbers per record are
-  u64 top = (ix->img.n > ix->img.e ? ix->img.n : ix->img.e);
-  int bits = 1;
-  while(bits < 64 && (top >> bits) != 0) { bits++; }
-  u64 *key_a = nullptr, *key_b = nullptr, *ranges = nullptr, *run_counts = nullptr, *run_off = nullptr;
-  u32 *perm_a = nullptr, *perm_b = nullptr, *head = nullptr, *run = nullptr;
-  unsigned long long* mult = nullptr;
-  char* tmp = nullptr;
-  HIP_TRY(scratch.get(key_a, c)); HIP_TRY(scratch.get(key_b, c));
-  HIP_TRY(scratch.get(perm_a, c)); HIP_TRY(scratch.get(perm_b, c));
-  HIP_TRY(scratch.get(head, c)); HIP_TRY(scratch.get(run, c)); HIP_TRY(scratch.get(run_of, c));
-  size_t sort_bytes = 0, scan_bytes = 0, sum_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, head, run, size_t(c), st));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, key_a, key_b, size_t(c + 1), st));
-  HIP_TRY(scratch.get(tmp, std::max(sort_bytes, std::max(scan_bytes, sum_bytes))));
-  hipLaunchKernelGGL(k_support_iota, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, c);
-  LAUNCH_CHECK("k_support_iota");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, cep, key_a, perm_a, perm_b, size_t(c), 0, bits, st));      // perm_b: by ep
-  hipLaunchKernelGGL(k_support_gather, dim3(grid_for(c)), dim3(TPB), 0, st, csp, perm_b, c, key_a);
-  LAUNCH_CHECK("k_support_gather");
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, key_a, key_b, perm_b, perm_a, size_t(c), 0, bits, st));    // key_b, perm_a: by (sp, ep)
-  hipLaunchKernelGGL(k_support_heads, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, perm_a, c, head);
-  LAUNCH_CHECK("k_support_heads");
-  HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, scan_bytes, head, run, size_t(c), st));
-  hipLaunchKernelGGL(k_classes_run_of, dim3(grid_for(c)), dim3(TPB), 0, st, perm_a, run, c, run_of);
-  LAUNCH_CHECK("k_classes_run_of");
-  u32 d32 = 0;
-  HIP_TRY(hipMemcpyAsync(&d32, run + (c - 1), sizeof(u32), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const u64 d = d32;
-  st_out->distinct = d;
-  HIP_TRY(scratch.get(ranges, 2 * d)); HIP_TRY(scratch.get(run_counts, d + 1)); HIP_TRY(scratch.get(run_off, d + 1)); HIP_TRY(scratch.get(mult, d));
-  HIP_TRY(scratch.get(span, 2 * d));
-  HIP_TRY(hipMemsetAsync(mult, 0, d * sizeof(unsigned long long), st));
-  HIP_TRY(hipMemsetAsync(span, 0, 2 * d * sizeof(u64), st));
-  HIP_TRY(hipMemsetAsync(run_counts + d, 0, sizeof(u64), st));
-  hipLaunchKernelGGL(k_support_runs, dim3(grid_for(c)), dim3(TPB), 0, st, key_b, cep, ccnt, static_cast<const u64*>(nullptr), perm_a, run, c, ranges, run_counts, mult);
-  LAUNCH_CHECK("k_support_runs");
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, sum_bytes, run_counts, run_off, size_t(d + 1), st));
+  if(fold.counted == 0) { return vote(); }
   // 3. the chunks, as support_tail cuts them
-  const u64 budget = support_chunk_budget();
-  struct Chunk { u64 q0, q1, raw; };
-  std::vector<Chunk> chunks;
-  unsigned long long* d_cut = stat + CLS_CUT;
-  u64 most_runs = 0, most_raw = 0, all_raw = 0;
-  for(u64 q0 = 0; q0 < d; )
-  {
-    unsigned long long cut[2] = {0, 0};
-    hipLaunchKernelGGL(k_support_cut, dim3(1), dim3(1), 0, st, run_off, d, q0, budget, ix->tune.locate_split_queries, d_cut);
-    LAUNCH_CHECK("k_support_cut");
-    HIP_TRY(hipMemcpyAsync(cut, d_cut, sizeof(cut), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const u64 q1 = cut[0], raw = cut[1];
-    if(q1 <= q0 || q1 > d) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "classes: a chunk without a range"); }
-    chunks.push_back(Chunk{q0, q1, raw});
-    most_runs = std::max(most_runs, q1 - q0); most_raw = std::max(most_raw, raw); all_raw += raw;
-    q0 = q1;
-  }
+  SeedChunks chunks;
+  rc = cut_chunks(ix, fold, stat + CLS_CUT, "classes", chunks, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
   // 4. locate and sign, chunk by chunk, in the same scratch; the signatures of all chunks stay, one entry per value at most
-  u64 *off = nullptr, *val = nullptr, *owners = nullptr, *keys = nullptr, *sorted = nullptr;
+  const u64 most_raw = chunks.most_raw, most_runs = chunks.most_runs;
+  u64 *keys = nullptr, *sorted = nullptr;
   u32 *lengths = nullptr, *n_entries = nullptr;
   char* cub = nullptr;
   if(most_raw >= (u64(1) << 31)) { scratch.settled = true; return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "classes: a range with 2^31 or more values; set hit_max"); }
-  HIP_TRY(scratch.get(off, most_runs + 1)); HIP_TRY(scratch.get(val, most_raw)); HIP_TRY(scratch.get(owners, most_raw / OWNER_SPAN + 3));
-  HIP_TRY(scratch.get(keys, most_raw)); HIP_TRY(scratch.get(sorted, most_raw)); HIP_TRY(scratch.get(lengths, most_raw)); HIP_TRY(scratch.get(n_entries, 1));
-  HIP_TRY(scratch.get(sig, all_raw));
-  int run_bits = 1;
-  while(run_bits < 50 && (most_runs >> run_bits) != 0) { run_bits++; }
   const bool wide = job.top_n != 0;
-  if(wide && most_runs >= (u64(1) << 31)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "top_classes: a chunk with 2^31 or more ranges"); }
-  const int key_bits = int(wide ? WIDE_KEY_BITS : CLASS_KEY_BITS) + run_bits;
+  int key_bits = 0;
   size_t keys_bytes = 0, rle_bytes = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, keys_bytes, keys, sorted, size_t(most_raw > 0 ? most_raw : 1), 0, key_bits, st));
-  HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, sorted, keys, lengths, n_entries, int(most_raw > 0 ? most_raw : 1), st));
-  HIP_TRY(scratch.get(cub, std::max(keys_bytes, rle_bytes)));
-  u64 values = 0;
-  for(const Chunk& chunk : chunks)
+  rc = for_located_chunks(ix, fold, chunks, "classes", &st_out->values, scratch, st, [&]() -> int
   {
-    const u64 runs = chunk.q1 - chunk.q0;
-    u64 total = 0;
-    ValuesProvider provide = [val, most_raw](u64 count) -> u64* { return count <= most_raw ? val : nullptr; };
-    const int rc = locate_core(ix, ranges + 2 * chunk.q0, runs, 1, off, provide, &total, st, val, most_raw);
-    if(rc != GCSA2_OK) { return rc; }
-    if(total == 0) { continue; }
-    if(total > most_raw || values + total > all_raw) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "classes: a chunk with more values than its ranges count"); }
-    const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
-    hipLaunchKernelGGL(k_block_owners, dim3(grid_for(spans + 1)), dim3(TPB), 0, st, off, runs, total, OWNER_SPAN, spans, owners);
-    LAUNCH_CHECK("k_block_owners");
-    if(wide) { hipLaunchKernelGGL(k_classes_keys_wide, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, job.n_classes, keys); }
-    else { hipLaunchKernelGGL(k_classes_keys, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, u32(job.n_classes), keys); }
+    HIP_TRY(scratch.get(keys, most_raw)); HIP_TRY(scratch.get(sorted, most_raw)); HIP_TRY(scratch.get(lengths, most_raw)); HIP_TRY(scratch.get(n_entries, 1));
+    HIP_TRY(scratch.get(sig, chunks.all_raw));
+    int run_bits = 1;
+    while(run_bits < 50 && (most_runs >> run_bits) != 0) { run_bits++; }
+    if(wide && most_runs >= (u64(1) << 31)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "top_classes: a chunk with 2^31 or more ranges"); }
+    key_bits = int(wide ? WIDE_KEY_BITS : CLASS_KEY_BITS) + run_bits;
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, keys_bytes, keys, sorted, size_t(most_raw > 0 ? most_raw : 1), 0, key_bits, st));
+    HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, sorted, keys, lengths, n_entries, int(most_raw > 0 ? most_raw : 1), st));
+    HIP_TRY(scratch.get(cub, std::max(keys_bytes, rle_bytes)));
+    return GCSA2_OK;
+  },
+  [&](const SeedChunk& chunk, u64, u64 total, const u64* off, const u64* val, const u64* owners, u64 values) -> int
+  {
+    if(wide) { hipLaunchKernelGGL(k_classes_keys<true>, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, job.n_classes, keys); }
+    else { hipLaunchKernelGGL(k_classes_keys<false>, dim3(grid_for(total)), dim3(TPB), 0, st, off, val, owners, total, u32(job.shift), job.class_of_bin, job.n_bins, u32(job.n_classes), keys); }
     LAUNCH_CHECK("k_classes_keys");
     scratch.settled = false;
     HIP_TRY(hipcub::DeviceRadixSort::SortKeys(cub, keys_bytes, keys, sorted, size_t(total), 0, key_bits, st));
     HIP_TRY(hipcub::DeviceRunLengthEncode::Encode(cub, rle_bytes, sorted, keys, lengths, n_entries, int(total), st));
-    if(wide) { hipLaunchKernelGGL(k_classes_sign_wide, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span); }
-    else { hipLaunchKernelGGL(k_classes_sign, dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, span); }
+    hipLaunchKernelGGL((wide ? k_classes_sign<true> : k_classes_sign<false>), dim3(grid_for(total)), dim3(TPB), 0, st, keys, lengths, n_entries, chunk.q0, values, sig, fold.span);
     LAUNCH_CHECK("k_classes_sign");
-    values += total;
-  }
-  st_out->values = values;
+    return GCSA2_OK;
+  });
+  if(rc != GCSA2_OK) { return rc; }
   // 5. the votes
   return vote();
 }
@@ -6207,15 +6082,10 @@ int kmer_classes_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const u
   if(rc != GCSA2_OK) { return rc; }
   if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  rc = kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+  return stats_entry(name, ix, stats, gcsa2_class_stats{}, n_patterns == 0, [&](gcsa2_class_stats& sums) -> int
+  {
+    return kmer_classes_core(ix, d_patterns, d_offsets, n_patterns, k, stride, job, &sums, static_cast<hipStream_t>(stream));
+  });
 }
 
 // gcsa2_seed_classes_device and gcsa2_seed_top_classes_device, likewise
@@ -6228,22 +6098,16 @@ int seed_classes_entry(const gcsa2_index* ix, const uint64_t* d_group_offsets, u
   if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_seeds is NULL"); }
   if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more groups in one call; split the batch"); }
   if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more seeds in one call; split the batch"); }
-  gcsa2_class_stats sums{};
-  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.windows = n_seeds;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
+  gcsa2_class_stats pre{};
+  pre.windows = n_seeds;
+  return stats_entry(name, ix, stats, pre, n_groups == 0, [&](gcsa2_class_stats& sums) -> int
   {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
     Scratch scratch(ix, st);
-    rc = classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
-                      job, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+    return classes_tail(ix, reinterpret_cast<const u64*>(d_seeds), 5, nullptr, d_weights, n_seeds, false, d_group_offsets, n_groups, n_seeds, nullptr, nullptr,
+                        job, &sums, scratch, st);
+  });
 }
 
 // The host form.  The class map goes to the device once; each piece (for_read_pieces) is one gcsa2_kmer_classes_device on its
@@ -6293,11 +6157,7 @@ int classes_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t
     return true;
   });
   if(rc != GCSA2_OK) { return rc; }
-  for(const gcsa2_class_stats& s : done)
-  {
-    sums.windows += s.windows; sums.found += s.found; sums.counted += s.counted; sums.distinct += s.distinct; sums.values += s.values;
-    sums.votes += s.votes; sums.unclassified += s.unclassified; sums.ambiguous += s.ambiguous;
-  }
+  for(const gcsa2_class_stats& s : done) { sum_stats(sums, s); }
   if(stats != nullptr) { *stats = sums; }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
@@ -6386,13 +6246,8 @@ int clusters_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, 
 // CLU_CAP_MIN to CLU_CAP_DEFAULT; anything else is ignored.  No result but stats.spilled depends on it.
 u32 cluster_capacity()
 {
-  const char* env = std::getenv("GCSA2_CLUSTER_LDS");
-  if(env != nullptr && *env != 0)
-  {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(env, &end, 10);
-    if(end != env && *end == 0 && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
-  }
+  u64 v = 0;
+  if(env_count("GCSA2_CLUSTER_LDS", &v) && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
   return CLU_CAP_DEFAULT;
 }
 
@@ -6556,16 +6411,12 @@ int fused_clusters_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const
   if(rc != GCSA2_OK) { return rc; }
   if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
   if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_cluster_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.groups = n_patterns;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  rc = fused_clusters_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_") + name + "_device: " + e.what()); }
+  gcsa2_cluster_stats pre{};
+  pre.groups = n_patterns;
+  return stats_entry(name, ix, stats, pre, n_patterns == 0, [&](gcsa2_cluster_stats& sums) -> int
+  {
+    return fused_clusters_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
+  });
 }
 
 // Both host forms.  The coordinate map goes to the device once; each piece (for_read_pieces) is one fused device call on its
@@ -6615,11 +6466,7 @@ int clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_
     return true;
   });
   if(rc != GCSA2_OK) { return rc; }
-  for(const gcsa2_cluster_stats& s : done)
-  {
-    sums.groups += s.groups; sums.invalid_groups += s.invalid_groups; sums.seeds += s.seeds; sums.anchors += s.anchors; sums.unplaced += s.unplaced;
-    sums.clusters += s.clusters; sums.spilled += s.spilled;
-  }
+  for(const gcsa2_cluster_stats& s : done) { sum_stats(sums, s); }
   if(stats != nullptr) { *stats = sums; }
   return GCSA2_OK;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
@@ -6643,21 +6490,15 @@ int gcsa2_seed_clusters_device(const gcsa2_index* ix, const uint64_t* d_group_of
   if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more groups in one call; split the batch"); }
   if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more seeds in one call; split the batch"); }
   if(n_hits >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more hits in one call; split the batch"); }
-  gcsa2_cluster_stats sums{};
-  if(n_groups == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  sums.groups = n_groups;
-  try {   // no C++ exception may cross the C boundary
-  DeviceGuard guard(ix->device);
-  g_error.clear();
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  gcsa2_cluster_stats pre{};
+  pre.groups = n_groups;
+  return stats_entry("seed_clusters", ix, stats, pre, n_groups == 0, [&](gcsa2_cluster_stats& sums) -> int
   {
+    hipStream_t st = static_cast<hipStream_t>(stream);
     Scratch scratch(ix, st);
     const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
-    rc = clusters_core(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, job, &sums, scratch, st);
-  }
-  if(rc == GCSA2_OK && stats != nullptr) { *stats = sums; }
-  return rc;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_seed_clusters_device: ") + e.what()); }
+    return clusters_core(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, job, &sums, scratch, st);
+  });
 }
 
 int gcsa2_kmer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,

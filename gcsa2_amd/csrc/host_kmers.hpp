@@ -269,14 +269,8 @@ constexpr u64 SPECTRUM_EMIT_PIECE = u64(1) << 24;     // records of one piece: 1
 // gridDim.x-th tile of 256 states.  The result never depends on it.
 u64 spectrum_leaf_groups(const gcsa2_index* ix)
 {
-  u64 groups = u64(ix->compute_units) * SPECTRUM_LEAF_GROUPS_PER_CU;
-  const char* env = std::getenv("GCSA2_SPECTRUM_GROUPS");
-  if(env != nullptr && *env != 0)
-  {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(env, &end, 10);
-    if(end != env && *end == 0 && v >= 1) { groups = v; }
-  }
+  u64 groups = u64(ix->compute_units) * SPECTRUM_LEAF_GROUPS_PER_CU, v = 0;
+  if(env_count("GCSA2_SPECTRUM_GROUPS", &v) && v >= 1) { groups = v; }
   return std::min(groups, u64(1) << 31);
 }
 

@@ -3,15 +3,16 @@
 // search, fold and chunked locate, but the sums stay with the read.  Included by gcsa2_hip.hip after kernels_support.hpp
 // (k_support_iota / gather / heads / runs / cut, wave_sum) and kernels_locate.hpp (count_range, k_block_owners, owner_in_wave).
 //
-// Data flow: k_classes_fold (k_support_class's cap and compaction; additionally every record keeps its compacted place or
-// "not counted") -> the sorts, heads and runs of kernels_support.hpp, unchanged -> k_classes_run_of (compacted place -> run) ->
-// per chunk of runs locate_core(sort = 1), k_classes_keys (one key (run, class) per located value), a radix sort and a
-// run-length encoding of the keys (hipCUB), k_classes_sign (the encoded keys become the runs' SIGNATURES: per run the list of
-// (class, n_c) with n_c > 0, the values without a class last) -> k_classes_vote (one wavefront per read: its records look up
-// run -> signature and add into a row of 64-bit counters in LDS; the row and the call leave with plain stores).
+// Data flow: fold_seed_ranges with slots (host_fold.hpp) -- k_seed_cap<true> (the cap and compaction of k-mer support; instead
+// of a weight every record keeps its compacted place or "not counted") -> the sorts, heads and runs of
+// kernels_support.hpp, unchanged -> k_classes_run_of (compacted place -> run) -- then cut_chunks and, per chunk of runs,
+// for_located_chunks -- locate_core(sort = 1), k_block_owners -- and k_classes_keys (one key (run, class) per located value), a
+// radix sort and a run-length encoding of the keys (hipCUB), k_classes_sign (the encoded keys become the runs' SIGNATURES: per
+// run the list of (class, n_c) with n_c > 0, the values without a class last) -> k_classes_vote (one wavefront per read: its
+// records look up run -> signature and add into a row of 64-bit counters in LDS; the row and the call leave with plain stores).
 // The signatures of all runs are kept: at most one entry per distinct located value, whatever the number of records.
-// The sparse form (gcsa2_kmer_top_classes_device, gcsa2_seed_top_classes_device) takes the same way with the wide twins of the
-// key and signature kernels and ends in k_classes_top (a hash table in LDS instead of the row; per read its top classes).
+// The sparse form (gcsa2_kmer_top_classes_device, gcsa2_seed_top_classes_device) takes the same way with the WIDE instances of
+// the key and signature kernels and ends in k_classes_top (a hash table in LDS instead of the row; per read its top classes).
 #pragma once
 
 namespace {
@@ -20,55 +21,15 @@ namespace {
 // CLS_CUT: two words, k_support_cut's answer)
 enum : u32 { CLS_CURSOR = 0, CLS_VOTES = 1, CLS_UNCLASSIFIED = 2, CLS_AMBIGUOUS = 3, CLS_CUT = 4, CLS_WORDS = 8 };
 
-constexpr u32 CLASS_SLOT_NONE = 0xFFFFFFFFu;       // a record that is not counted (compacted places stay below: fewer than 2^32 records)
 constexpr u32 CLASS_KEY_BITS = 13;                 // a key is run << 13 | class, class 0 .. 4095 or CLASS_KEY_NONE
 constexpr u32 CLASS_KEY_NONE = 4096;               // "no class": sorts behind every class of its run
 static_assert(GCSA2_CLASS_LIMIT == CLASS_KEY_NONE, "a class id and `no class` fit the key's low bits");
-constexpr u32 CLASSES_FOLD_TPB = 1024;
-
-// k_support_class with one more output: slot[i] = the compacted place of record i, or CLASS_SLOT_NONE when it is not counted.
-// No weights travel: a vote is weighted by the record that casts it, not by its run.  One atomic per workgroup.
-__global__ __launch_bounds__(CLASSES_FOLD_TPB) void k_classes_fold(DevImage img, const u64* __restrict__ recs, u32 words, const u64* __restrict__ known,
-                                                                   u64 m, u64 hit_max, unsigned long long* __restrict__ stat, u64* __restrict__ sp_out,
-                                                                   u64* __restrict__ ep_out, u64* __restrict__ count_out, u32* __restrict__ slot)
-{
-  constexpr u32 WAVES = CLASSES_FOLD_TPB / 64;
-  __shared__ u32 wave_counted[WAVES], wave_found[WAVES];
-  __shared__ u64 group_base;
-  const u64 i = u64(blockIdx.x) * CLASSES_FOLD_TPB + threadIdx.x;
-  const u32 lane = threadIdx.x & 63, wave = threadIdx.x / 64;
-  u64 sp = 0, ep = 0, count = 0;
-  bool found = false, counted = false;
-  if(i < m)
-  {
-    sp = recs[u64(words) * i + 2]; ep = recs[u64(words) * i + 3];
-    found = !range_empty(sp, ep);
-    if(found)
-    {
-      count = (known != nullptr ? known[i] : count_range(img, sp, ep));
-      counted = (count != 0 && (hit_max == 0 || count <= hit_max));
-    }
-  }
-  const u64 f = __ballot(found), c = __ballot(counted);
-  if(lane == 0) { wave_found[wave] = u32(__popcll(f)); wave_counted[wave] = u32(__popcll(c)); }
-  __syncthreads();
-  if(threadIdx.x == 0)
-  {
-    u64 all_found = 0, all_counted = 0;
-    for(u32 w = 0; w < WAVES; w++) { all_found += wave_found[w]; all_counted += wave_counted[w]; }
-    const u64 word = (all_found << 32) | all_counted;
-    group_base = (word != 0 ? u64(atomicAdd(stat + CLS_CURSOR, (unsigned long long)word)) & 0xFFFFFFFFull : 0);
-  }
-  __syncthreads();
-  if(counted)
-  {
-    u64 at = group_base + u64(__popcll(c & ((u64(1) << lane) - 1)));        // at < m: no more places are reserved than records exist
-    for(u32 w = 0; w < wave; w++) { at += wave_counted[w]; }
-    sp_out[at] = sp; ep_out[at] = ep; count_out[at] = count;
-    slot[i] = u32(at);
-  }
-  else if(i < m) { slot[i] = CLASS_SLOT_NONE; }
-}
+// The wide keys of gcsa2_kmer_top_classes_device: a class id of 32 bits, so a key is run << 33 | class with "no class" =
+// 2^32 behind every class of its run (a chunk has fewer than 2^31 runs), and a signature entry n_c << 32 | class with
+// 0xFFFFFFFF for "no class" (a class id is below n_classes <= 0xFFFFFFFF).
+constexpr u32 WIDE_KEY_BITS = 33;
+constexpr u64 WIDE_KEY_NONE = u64(1) << 32;
+constexpr u32 WIDE_SIG_NONE = 0xFFFFFFFFu;
 
 // perm: the compacted place of the record at sorted place i; run: the inclusive scan of the heads.  run_of[place] = its run.
 __global__ __launch_bounds__(TPB) void k_classes_run_of(const u32* __restrict__ perm, const u32* __restrict__ run, u64 count, u32* __restrict__ run_of)
@@ -79,74 +40,42 @@ __global__ __launch_bounds__(TPB) void k_classes_run_of(const u32* __restrict__ 
 
 // One lane per located value of a chunk of runs (offsets / values / owners as in k_support_add): its key, the run inside the
 // chunk above the class of the value's bin.  A bin beyond the map and a class id >= n_classes (GCSA2_CLASS_NONE among them)
-// are "no class".  The bin is taken unsigned.
+// are "no class".  The bin is taken unsigned.  WIDE: the wide key, and n_classes of 64 bits.
+template<bool WIDE>
 __global__ __launch_bounds__(TPB) void k_classes_keys(const u64* __restrict__ offsets, const u64* __restrict__ values, const u64* __restrict__ owners,
-                                                      u64 total, u32 shift, const u32* __restrict__ class_of_bin, u64 n_bins, u32 n_classes,
-                                                      u64* __restrict__ keys)
+                                                      u64 total, u32 shift, const u32* __restrict__ class_of_bin, u64 n_bins,
+                                                      std::conditional_t<WIDE, u64, u32> n_classes, u64* __restrict__ keys)
 {
   const u64 j = u64(blockIdx.x) * TPB + threadIdx.x;
   const bool live = j < total;
   const u64 r = owner_in_wave(owners, offsets, total, live ? j : 0, live);
   if(!live) { return; }
   const u64 bin = values[j] >> shift;
-  u32 cls = CLASS_KEY_NONE;
+  std::conditional_t<WIDE, u64, u32> cls = (WIDE ? WIDE_KEY_NONE : CLASS_KEY_NONE);
   if(bin < n_bins)
   {
     const u32 id = class_of_bin[bin];
     if(id < n_classes) { cls = id; }
   }
-  keys[j] = (r << CLASS_KEY_BITS) | cls;
+  keys[j] = (r << (WIDE ? WIDE_KEY_BITS : CLASS_KEY_BITS)) | cls;
 }
 
 // The chunk's sorted keys, run-length encoded: `unique` keys with their `lengths`, *n_entries of them.  Entry e becomes the
-// signature entry n_c << 32 | class at sig[base + e]; the first and the last entry of a run write the run's span
-// {begin, end} of entries (zeroed beforehand: a run without a value has the empty span).  q0: the chunk's first run.
+// signature entry n_c << 32 | class (WIDE: WIDE_SIG_NONE for "no class") at sig[base + e]; the first and the last entry of a
+// run write the run's span {begin, end} of entries (zeroed beforehand: a run without a value has the empty span).  q0: the
+// chunk's first run.
+template<bool WIDE>
 __global__ __launch_bounds__(TPB) void k_classes_sign(const u64* __restrict__ unique, const u32* __restrict__ lengths, const u32* __restrict__ n_entries,
                                                       u64 q0, u64 base, u64* __restrict__ sig, u64* __restrict__ span)
 {
+  constexpr u32 BITS = (WIDE ? WIDE_KEY_BITS : CLASS_KEY_BITS);
   const u64 e = u64(blockIdx.x) * TPB + threadIdx.x, n = *n_entries;
   if(e >= n) { return; }
-  const u64 key = unique[e], run = key >> CLASS_KEY_BITS;
-  sig[base + e] = (u64(lengths[e]) << 32) | (key & ((u64(1) << CLASS_KEY_BITS) - 1));
-  if(e == 0 || (unique[e - 1] >> CLASS_KEY_BITS) != run) { span[2 * (q0 + run)] = base + e; }
-  if(e + 1 == n || (unique[e + 1] >> CLASS_KEY_BITS) != run) { span[2 * (q0 + run) + 1] = base + e + 1; }
-}
-
-// The wide twins for gcsa2_kmer_top_classes_device: a class id of 32 bits, so a key is run << 33 | class with "no class" =
-// 2^32 behind every class of its run (a chunk has fewer than 2^31 runs), and a signature entry n_c << 32 | class with
-// 0xFFFFFFFF for "no class" (a class id is below n_classes <= 0xFFFFFFFF).
-constexpr u32 WIDE_KEY_BITS = 33;
-constexpr u64 WIDE_KEY_NONE = u64(1) << 32;
-constexpr u32 WIDE_SIG_NONE = 0xFFFFFFFFu;
-
-__global__ __launch_bounds__(TPB) void k_classes_keys_wide(const u64* __restrict__ offsets, const u64* __restrict__ values, const u64* __restrict__ owners,
-                                                           u64 total, u32 shift, const u32* __restrict__ class_of_bin, u64 n_bins, u64 n_classes,
-                                                           u64* __restrict__ keys)
-{
-  const u64 j = u64(blockIdx.x) * TPB + threadIdx.x;
-  const bool live = j < total;
-  const u64 r = owner_in_wave(owners, offsets, total, live ? j : 0, live);
-  if(!live) { return; }
-  const u64 bin = values[j] >> shift;
-  u64 cls = WIDE_KEY_NONE;
-  if(bin < n_bins)
-  {
-    const u32 id = class_of_bin[bin];
-    if(id < n_classes) { cls = id; }
-  }
-  keys[j] = (r << WIDE_KEY_BITS) | cls;
-}
-
-__global__ __launch_bounds__(TPB) void k_classes_sign_wide(const u64* __restrict__ unique, const u32* __restrict__ lengths, const u32* __restrict__ n_entries,
-                                                           u64 q0, u64 base, u64* __restrict__ sig, u64* __restrict__ span)
-{
-  const u64 e = u64(blockIdx.x) * TPB + threadIdx.x, n = *n_entries;
-  if(e >= n) { return; }
-  const u64 key = unique[e], run = key >> WIDE_KEY_BITS;
-  const u64 cls = key & ((u64(1) << WIDE_KEY_BITS) - 1);
-  sig[base + e] = (u64(lengths[e]) << 32) | (cls == WIDE_KEY_NONE ? u64(WIDE_SIG_NONE) : cls);
-  if(e == 0 || (unique[e - 1] >> WIDE_KEY_BITS) != run) { span[2 * (q0 + run)] = base + e; }
-  if(e + 1 == n || (unique[e + 1] >> WIDE_KEY_BITS) != run) { span[2 * (q0 + run) + 1] = base + e + 1; }
+  const u64 key = unique[e], run = key >> BITS;
+  const u64 cls = key & ((u64(1) << BITS) - 1);
+  sig[base + e] = (u64(lengths[e]) << 32) | (WIDE && cls == WIDE_KEY_NONE ? u64(WIDE_SIG_NONE) : cls);
+  if(e == 0 || (unique[e - 1] >> BITS) != run) { span[2 * (q0 + run)] = base + e; }
+  if(e + 1 == n || (unique[e + 1] >> BITS) != run) { span[2 * (q0 + run) + 1] = base + e + 1; }
 }
 
 // (votes, class) a ahead of b: more votes, the lower id on a tie.  A lane without a candidate holds (0, GCSA2_UNKNOWN).
@@ -192,7 +121,7 @@ __global__ __launch_bounds__(64) void k_classes_vote(const u64* __restrict__ gro
         rec = u64(wave_base[i / 64]) + u64(__popcll(mask & (bit - 1)));
       }
       const u32 place = slot[rec];
-      if(place == CLASS_SLOT_NONE) { continue; }
+      if(place == SEED_SLOT_NONE) { continue; }
       counted++;
       const u32 r = run_of[place];
       const u64 first = span[2 * u64(r)], last = span[2 * u64(r) + 1];
@@ -324,7 +253,7 @@ __global__ __launch_bounds__(64) void k_classes_top(const u64* __restrict__ grou
             rec = u64(wave_base[i / 64]) + u64(__popcll(mask & (bit - 1)));
           }
           const u32 place = slot[rec];
-          if(place == CLASS_SLOT_NONE) { continue; }
+          if(place == SEED_SLOT_NONE) { continue; }
           counted++;
           const u32 r = run_of[place];
           const u64 first = span[2 * u64(r)], last = span[2 * u64(r) + 1];

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(TPB) void k_kmer_compare(const DevImage* __restrict
 enum : u32 { SPEC_KMERS = 0, SPEC_NODES = 1, SPEC_OCCURRENCES = 2, SPEC_UNIQUE = 3, SPEC_MAX = 4, SPEC_CURSOR = 5, SPEC_WORDS = 8 };
 
 // what the leaf kernel writes besides the sums: the histogram alone, gcsa2_mem records {0, k, sp, ep, count()} of every state
-// with their count()s in an array of their own (the `known` of k_support_class), or gcsa2_index_kmer records of the states
+// with their count()s in an array of their own (the `known` of k_seed_cap), or gcsa2_index_kmer records of the states
 // whose value lies in a window
 enum : int { SPEC_HISTOGRAM = 0, SPEC_SEEDS = 1, SPEC_LIST = 2 };
 

@@ -1,10 +1,12 @@
 // kernels_support.hpp -- k-mer support (gcsa2_kmer_support_device, gcsa2_seed_support_device): seed records in any order
 // become per-bin sums.  Included by gcsa2_hip.hip after kernels_locate.hpp (count_range, k_block_owners, owner_in_wave).
 //
-// Data flow: k_support_class (one lane per record: count(), the cap, the counted records compacted in arrival order) ->
-// two stable radix passes by ep, then sp (hipCUB) -> k_support_heads + an inclusive scan (the run number of every record) ->
-// k_support_runs (per run {sp, ep}, count() and the summed weight) -> a scan of the runs' count() -> per chunk of runs
-// locate_core(sort = 1) into scratch of the chunk's size, k_block_owners over its value offsets, k_support_add.
+// Data flow, the host side of which is host_fold.hpp up to the last kernel: fold_seed_ranges -- k_seed_cap (one lane per
+// record: count(), the cap, the counted records compacted in arrival order) -> two stable radix passes by ep, then sp
+// (hipCUB) -> k_support_heads + an inclusive scan (the run number of every record) -> k_support_runs (per run {sp, ep},
+// count() and the summed weight) -> a scan of the runs' count() -- then cut_chunks (k_support_cut) and, per chunk of runs,
+// for_located_chunks -- locate_core(sort = 1) into scratch of the chunk's size, k_block_owners over its value offsets -- and
+// k_support_add.  k-mer classes (kernels_classes.hpp) take the same way to their own last kernels.
 // Nothing here is kept in an order the caller sees; the sums are integers, so the result does not depend on arrival.
 #pragma once
 
@@ -40,25 +42,36 @@ __device__ __forceinline__ u64 wave_run_sum(u64 key, u64 v, u32 lane, bool& tail
   return v;
 }
 
+// The cap and the compaction of both consumers of seed records: k_seed_cap<false, const u64*> for k-mer support,
+// k_seed_cap<true> for k-mer classes (kernels_classes.hpp).
 // One lane per record: `words` u64 per record with (sp, ep) at words 2 and 3 (4: the arrival records of k_kmer_seeds, whose
 // count() is known[i]; 5: gcsa2_mem, whose count field is NOT read -- count() is evaluated here).  found: a non-empty range;
 // counted: found, count() != 0 (a range that reaches beyond the index has none) and hit_max == 0 or count() <= hit_max.  The
 // counted lanes of a workgroup are ranked -- a ballot per wavefront, the wavefronts' numbers through LDS -- and the workgroup
 // reserves their places with ONE atomic add on stat[SUP_CURSOR], which carries the found records in its high half (both
-// numbers stay below 2^32); the lanes leave (sp, ep, count(), weight) at their places, in arrival order between workgroups.
+// numbers stay below 2^32); the lanes leave (sp, ep, count()) at their places, in arrival order between workgroups.
+// What else a record leaves follows SLOTS.  false: its weight at its place, out[place] = weights[i], when `out` is there.
+// true: out[i] = the compacted place of record i, or SEED_SLOT_NONE when it is not counted; no weights travel (a vote is
+// weighted by the record that casts it, not by its run), and the kernel has no such parameter: `Weights` is empty.  That is
+// why the weights are a pack -- an instance's argument offsets are part of its code, and with its own parameter list each
+// instance is, instruction for instruction, the kernel it replaced (k_support_class, k_classes_fold;
+// profiles/seed_fold_refactor.md).
 // (The first form had every wavefront add to three counters of one cache line: 6.3 M atomics on three addresses were 75 ms
 // of a 115 ms call on 135 M records; profiles/kmer_support.md.)
-constexpr u32 SUPPORT_CLASS_TPB = 1024;
+constexpr u32 SEED_CAP_TPB = 1024;
+constexpr u32 SEED_SLOT_NONE = 0xFFFFFFFFu;        // a record that is not counted (compacted places stay below: fewer than 2^32 records)
 
-__global__ __launch_bounds__(SUPPORT_CLASS_TPB) void k_support_class(DevImage img, const u64* __restrict__ recs, u32 words, const u64* __restrict__ known,
-                                                                     const u64* __restrict__ weights, u64 m, u64 hit_max, unsigned long long* __restrict__ stat,
-                                                                     u64* __restrict__ sp_out, u64* __restrict__ ep_out, u64* __restrict__ count_out,
-                                                                     u64* __restrict__ weight_out)
+template<bool SLOTS, class... Weights>
+__global__ __launch_bounds__(SEED_CAP_TPB) void k_seed_cap(DevImage img, const u64* __restrict__ recs, u32 words, const u64* __restrict__ known,
+                                                           Weights __restrict__... weights, u64 m, u64 hit_max, unsigned long long* __restrict__ stat,
+                                                           u64* __restrict__ sp_out, u64* __restrict__ ep_out, u64* __restrict__ count_out,
+                                                           std::conditional_t<SLOTS, u32, u64>* __restrict__ out)
 {
-  constexpr u32 WAVES = SUPPORT_CLASS_TPB / 64;
+  static_assert(sizeof...(Weights) == (SLOTS ? 0 : 1), "the weights travel exactly when the slots do not");
+  constexpr u32 WAVES = SEED_CAP_TPB / 64;
   __shared__ u32 wave_counted[WAVES], wave_found[WAVES];
   __shared__ u64 group_base;
-  const u64 i = u64(blockIdx.x) * SUPPORT_CLASS_TPB + threadIdx.x;
+  const u64 i = u64(blockIdx.x) * SEED_CAP_TPB + threadIdx.x;
   const u32 lane = threadIdx.x & 63, wave = threadIdx.x / 64;
   u64 sp = 0, ep = 0, count = 0;
   bool found = false, counted = false;
@@ -88,8 +101,10 @@ __global__ __launch_bounds__(SUPPORT_CLASS_TPB) void k_support_class(DevImage im
     u64 at = group_base + u64(__popcll(c & ((u64(1) << lane) - 1)));        // at < m: no more places are reserved than records exist
     for(u32 w = 0; w < wave; w++) { at += wave_counted[w]; }
     sp_out[at] = sp; ep_out[at] = ep; count_out[at] = count;
-    if(weight_out != nullptr) { weight_out[at] = weights[i]; }
+    if constexpr(SLOTS) { out[i] = u32(at); }
+    else if(out != nullptr) { out[at] = (weights, ...)[i]; }
   }
+  else if(SLOTS && i < m) { out[i] = SEED_SLOT_NONE; }
 }
 
 __global__ __launch_bounds__(TPB) void k_support_iota(u32* __restrict__ dst, u64 count)
