@@ -2837,7 +2837,11 @@ int gcsa2_locate_max_into(const gcsa2_index* ix, const uint64_t* d_ranges, uint6
     *out = d_values;
     return GCSA2_OK;
   };
-  return locate_max_core(ix, d_ranges, nq, max_positions, d_offsets, provide, total, static_cast<hipStream_t>(stream));
+  const int core_rc = locate_max_core(ix, d_ranges, nq, max_positions, d_offsets, provide, total, static_cast<hipStream_t>(stream));
+  // the core releases its stream-ordered scratch (hipFreeAsync) behind its last wait: "complete on return" is an idle stream
+  const hipError_t idle = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+  if(core_rc == GCSA2_OK && idle != hipSuccess) { return fail(GCSA2_ERR_HIP, std::string("gcsa2_locate_max_into: ") + hipGetErrorString(idle)); }
+  return core_rc;
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_locate_max_into: ") + e.what()); }
 }
 
@@ -6276,6 +6280,9 @@ int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gc
   unsigned long long host_stat[CLU_WORDS];
   HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  // (both refusals before the next launch: the stream is idle here, so the arena may go back as it is)
+  const u64 count = host_stat[CLU_LARGE];
+  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: more anchors than hits"); }
   // the groups in LDS: one wavefront each up to CLU_WAVE_MAX anchors, a workgroup of 256 lanes each above; a launch takes the
   // LDS of its largest group
   {
@@ -6304,8 +6311,6 @@ int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gc
     }
   }
   // the groups above the capacity
-  const u64 count = host_stat[CLU_LARGE];
-  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: more anchors than hits"); }
   if(count > 0)
   {
     u64 *loff = nullptr, *dk = nullptr, *pe = nullptr, *gk = nullptr, *ka = nullptr, *kb = nullptr, *sdk = nullptr, *spe = nullptr, *sgk = nullptr;

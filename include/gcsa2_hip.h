@@ -375,6 +375,8 @@ int gcsa2_mailbox_stats(const gcsa2_index* index, uint64_t* calls, uint64_t* lau
 /* ---- locate: GCSA::locate(range, results, append=false, sort) (src/gcsa.cpp:827-842) -------
  * Two calls, CSR output.  locate_run runs the whole query and keeps the result on the device
  * inside `*job`; locate_fetch copies the values (offsets[n_queries] of them) and frees the job.
+ * Both, and gcsa2_locate_device below, are complete on return: *total_values is read back, and the job's
+ * buffers are plain allocations (a device-wide wait), so nothing is left on `stream`.
  * sort != 0: sorted distinct values per query (removeDuplicates, utils.h:350-357), so
  *            offsets[q+1] - offsets[q] == count(range q).
  * sort == 0: values in path order, duplicates kept, exactly as the reference pushes them.
