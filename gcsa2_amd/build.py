@@ -68,11 +68,11 @@ CLI_OUT = os.path.join(HERE, "lib", "query_gcsa")
 
 
 def cli_deps(src):
-    """Everything a facade client is compiled from: its source, the C header and every header of the facade
+    """Everything a facade client is compiled from: its source, the C headers and every header of the facade
     (include/gcsa2_hip/gcsa.hpp is six #includes of include/gcsa/*.h -- VERDICT r04 #7)."""
     import glob
     inc = os.path.join(ROOT, "include")
-    return [src, os.path.join(inc, "gcsa2_hip.h")] + sorted(glob.glob(os.path.join(inc, "gcsa2_hip", "*.hpp")) + glob.glob(os.path.join(inc, "gcsa", "*.h")))
+    return [src] + sorted(glob.glob(os.path.join(inc, "*.h")) + glob.glob(os.path.join(inc, "gcsa2_hip", "*.hpp")) + glob.glob(os.path.join(inc, "gcsa", "*.h")))
 
 
 def build_cli(name, force=False):

@@ -24,6 +24,7 @@
 //   kernels_support.hpp k_support_*           GCSA::locate(range) of every distinct range of a batch, summed per node id (no counterpart)
 //   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
 //   kernels_clusters.hpp k_clusters_*         per read the top diagonal bands of its seed hits (no counterpart)
+//   kernels_chains.hpp  k_chains_*            per read the top colinear chains of its seed hits (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
 //   kernels_kmers.hpp   k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //                       k_kmer_compare        compareKMers               src/algorithms.cpp:505-616
@@ -34,6 +35,7 @@
 #include "sdsl_reader.hpp"
 #include "sdsl_writer.hpp"
 #include "../../include/gcsa2_hip.h"
+#include "../../include/gcsa2_hip_chains.h"
 
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -69,6 +71,7 @@ using namespace g2;
 #include "kernels_support.hpp"
 #include "kernels_classes.hpp"
 #include "kernels_clusters.hpp"
+#include "kernels_chains.hpp"
 #include "kernels_kmers.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
@@ -5700,7 +5703,7 @@ int gcsa2_capped_seeds_batch(const gcsa2_index* ix, const uint8_t* patterns, con
 
 }  // extern "C"
 
-// ==== the calls over seed records with statistics: k-mer support, k-mer classes, seed clusters ===============================
+// ==== the calls over seed records with statistics: k-mer support, k-mer classes, seed clusters, seed chains ===============================
 namespace {
 
 // The shell of gcsa2_<name>_device after its argument checks.  `empty` (no read, no group, no record): zeroed statistics and
@@ -5731,7 +5734,8 @@ void sum_stats(Stats& a, const Stats& b)
   std::memcpy(&a, x, sizeof(Stats));
 }
 static_assert(sizeof(gcsa2_support_stats) == 7 * sizeof(uint64_t) && sizeof(gcsa2_class_stats) == 8 * sizeof(uint64_t) &&
-              sizeof(gcsa2_cluster_stats) == 7 * sizeof(uint64_t), "sum_stats: a field of another type was added");
+              sizeof(gcsa2_cluster_stats) == 7 * sizeof(uint64_t) && sizeof(gcsa2_chain_stats) == 7 * sizeof(uint64_t),
+              "sum_stats: a field of another type was added");
 
 }  // namespace
 
@@ -6235,23 +6239,27 @@ struct ClustersJob
   gcsa2_cluster* top; gcsa2_cluster_summary* summaries;
 };
 
-// what every form refuses before any device is touched
-int clusters_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, u64 n_bins, u64 top_n, const char* map_name)
+// what every form refuses before any device is touched (`what` and `limit`: "chains" and its limit's name for the chain calls,
+// which share these refusals)
+int clusters_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, u64 n_bins, u64 top_n, const char* map_name, const char* what = "clusters",
+                    const char* limit = "GCSA2_CLUSTER_TOP_LIMIT")
 {
   CHECK_INDEX(ix);
-  if(top_n == 0 || top_n > GCSA2_CLUSTER_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: top_n must be 1 .. GCSA2_CLUSTER_TOP_LIMIT (64)"); }
-  if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: shift must be below 64"); }
-  if(n_bins == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "clusters: n_bins must be at least 1"); }
-  if(coord_of_bin == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string("clusters: ") + map_name + " is NULL"); }
+  const std::string head = std::string(what) + ": ";
+  if(top_n == 0 || top_n > GCSA2_CLUSTER_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, head + "top_n must be 1 .. " + limit + " (64)"); }
+  if(shift >= 64) { return fail(GCSA2_ERR_INVALID_ARGUMENT, head + "shift must be below 64"); }
+  if(n_bins == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, head + "n_bins must be at least 1"); }
+  if(coord_of_bin == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, head + map_name + " is NULL"); }
   return GCSA2_OK;
 }
 
-// GCSA2_CLUSTER_LDS (a test knob, read per call): the anchors of a group that k_clusters_lds holds, a power of two from
-// CLU_CAP_MIN to CLU_CAP_DEFAULT; anything else is ignored.  No result but stats.spilled depends on it.
-u32 cluster_capacity()
+// GCSA2_CLUSTER_LDS, and GCSA2_CHAIN_LDS for the chain calls (test knobs, read per call): the anchors of a group that
+// k_clusters_lds (k_chains_lds) holds, a power of two from CLU_CAP_MIN to CLU_CAP_DEFAULT; anything else is ignored.  No result
+// but stats.spilled depends on it.
+u32 cluster_capacity(const char* knob = "GCSA2_CLUSTER_LDS")
 {
   u64 v = 0;
-  if(env_count("GCSA2_CLUSTER_LDS", &v) && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
+  if(env_count(knob, &v) && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
   return CLU_CAP_DEFAULT;
 }
 
@@ -6369,19 +6377,20 @@ int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gc
   return GCSA2_OK;
 }
 
-// The fused forms after their argument checks (0 < n_patterns < 2^32): the windows (every stride-th, or the minimizers), the
-// hits call's own core behind them (kmer_hits_found) into scratch of this call, then the cluster core with the seed offsets
-// as the groups.  The hit buffer is sized by a guess -- four hits per window, no more than hit_max allows -- and a batch
-// beyond it runs the hits again with the size the first run reported.
-int fused_clusters_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
-                        u64 w, u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, gcsa2_cluster_stats* out, hipStream_t st)
+// What the fused cluster and chain forms run first, after their argument checks (0 < n_patterns < 2^32): the windows (every
+// stride-th, or the minimizers) and the hits call's own core behind them (kmer_hits_found) into scratch of this call.  The hit
+// buffer is sized by a guess -- four hits per window, no more than hit_max allows -- and a batch beyond it runs the hits again
+// with the size the first run reported.  `name` is the call's ("kmer_clusters"), `what` heads the refusal of 2^32 seeds or hits.
+struct FusedHits { u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0; gcsa2_mem* seeds = nullptr; };
+
+int fused_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
+               u64 w, u64 hash_seed, u64 hit_max, int over, const char* name, const char* what, FusedHits& out, hipStream_t st)
 {
-  Scratch scratch(ix, st);
   u64 *woff = nullptr, total = 0;
   gcsa2_minimizer* mins = nullptr;
-  int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, "minimizer_clusters", st,
+  int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, name, st,
                                           woff, mins, total)
-                       : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, "kmer_clusters", st, woff, total));
+                       : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, name, st, woff, total));
   if(rc != GCSA2_OK) { return rc; }
   u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0;
   gcsa2_mem* seeds = nullptr;
@@ -6402,8 +6411,24 @@ int fused_clusters_core(const gcsa2_index* ix, const uint8_t* d_patterns, const 
                          total, &m, hit_off, hit_values, room, &h, st);
   }
   if(rc != GCSA2_OK) { return rc; }
-  if(m >= (u64(1) << 32) || h >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "clusters: 2^32 or more seeds or hits in one call; split the batch"); }
-  return clusters_core(ix, seed_off, n_patterns, seeds, m, hit_off, hit_values, h, job, out, scratch, st);
+  if(m >= (u64(1) << 32) || h >= (u64(1) << 32))
+  {
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(what) + ": 2^32 or more seeds or hits in one call; split the batch");
+  }
+  out.seed_off = seed_off; out.seeds = seeds; out.hit_off = hit_off; out.hit_values = hit_values; out.m = m; out.h = h;
+  return GCSA2_OK;
+}
+
+// The fused cluster forms: fused_hits, then the cluster core with the seed offsets as the groups.
+int fused_clusters_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
+                        u64 w, u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, gcsa2_cluster_stats* out, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  FusedHits f;
+  const int rc = fused_hits(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over,
+                            (minimizers ? "minimizer_clusters" : "kmer_clusters"), "clusters", f, st);
+  if(rc != GCSA2_OK) { return rc; }
+  return clusters_core(ix, f.seed_off, n_patterns, f.seeds, f.m, f.hit_off, f.hit_values, f.h, job, out, scratch, st);
 }
 
 int fused_clusters_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
@@ -6537,6 +6562,307 @@ int gcsa2_minimizer_clusters_batch(const gcsa2_index* ix, const uint8_t* pattern
 {
   return clusters_batch(ix, patterns, offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, shift, coord_of_bin, n_bins, band, top_n, top, summaries, stats,
                         "gcsa2_minimizer_clusters_batch");
+}
+
+}  // extern "C"
+
+// ==== seed chains: per read (or group of seed records) the top colinear chains of its anchors (kernels_chains.hpp) ====
+namespace {
+
+// what a chains call places with, chains with and writes
+struct ChainsJob
+{
+  u64 shift; const u64* coord_of_bin; u64 n_bins;
+  const gcsa2_chain_params* params;
+  gcsa2_chain* top; gcsa2_chain_anchor* members; gcsa2_chain_summary* summaries;
+};
+
+// what every form refuses before any device is touched: the refusals of the cluster calls and those of the parameters
+int chains_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, u64 n_bins, const gcsa2_chain_params* p, const char* map_name)
+{
+  CHECK_INDEX(ix);
+  if(p == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: params is NULL"); }
+  const int rc = clusters_checks(ix, shift, coord_of_bin, n_bins, p->top_n, map_name, "chains", "GCSA2_CHAIN_TOP_LIMIT");
+  if(rc != GCSA2_OK) { return rc; }
+  if(p->lookback == 0 || p->lookback > GCSA2_CHAIN_LOOKBACK_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: lookback must be 1 .. GCSA2_CHAIN_LOOKBACK_LIMIT (64)"); }
+  if(p->match == 0 || p->match > 65536) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: match must be 1 .. 65536"); }
+  if(p->gap > 65536) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: gap must be at most 65536"); }
+  if(p->max_gap == 0 || p->max_gap >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: max_gap must be 1 .. 2^32 - 1"); }
+  if(p->min_score >= (u64(1) << 62)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: min_score must be below 2^62"); }
+  return GCSA2_OK;
+}
+
+// member_cap > 0 with n_groups top_n member_cap >= 2^32 (top_n is 1 .. 64 here; no product is formed that could wrap)
+int chains_member_check(const gcsa2_chain_params* p, u64 n_groups)
+{
+  if(p->member_cap > 0 && n_groups > 0 && p->member_cap > (u64(0xFFFFFFFF) / p->top_n) / n_groups)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "chains: member_cap: n_groups x top_n x member_cap must be below 2^32");
+  }
+  return GCSA2_OK;
+}
+
+// The chain core, laid out as clusters_core.  n_groups >= 1; n_groups, n_seeds, n_hits < 2^32.  Writes every row, member row
+// and summary and fills every field of *out but `groups`.  One host round trip (the plan's counters), then the end.  Scratch:
+// 16 bytes per group; for the large path 8 bytes per group and 80 bytes per anchor of a group above the capacity, and hipCUB's.
+int chains_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa2_mem* seeds, u64 n_seeds, const u64* hoff, const u64* hits, u64 n_hits,
+                const ChainsJob& job, gcsa2_chain_stats* out, Scratch& scratch, hipStream_t st)
+{
+  const u64* recs = reinterpret_cast<const u64*>(seeds);
+  const CluMap map{u32(job.shift), job.coord_of_bin, job.n_bins};
+  const gcsa2_chain_params& p = *job.params;
+  const ChnParams P{p.band, p.max_gap, p.match, p.gap, p.min_score, p.member_cap, u32(p.lookback), u32(p.top_n)};
+  gcsa2_chain_anchor* members = (p.member_cap > 0 ? job.members : nullptr);
+  const u32 cap = cluster_capacity("GCSA2_CHAIN_LDS");
+  unsigned long long* stat = nullptr;
+  u64 *info = nullptr, *lsize = nullptr;
+  HIP_TRY(scratch.get(stat, CLU_WORDS));
+  HIP_TRY(scratch.get(info, n_groups));
+  HIP_TRY(scratch.get(lsize, n_groups + 1));
+  HIP_TRY(hipMemsetAsync(stat, 0, CLU_WORDS * sizeof(unsigned long long), st));
+  scratch.settled = false;
+  const u64 resident = u64(ix->compute_units) * 8;
+  hipLaunchKernelGGL(k_clusters_plan, dim3(unsigned(std::min<u64>((n_groups + 3) / 4, resident))), dim3(TPB), 0, st, goff, n_groups, n_seeds, hoff, n_hits,
+                     u64(cap), info, lsize, stat);
+  LAUNCH_CHECK("k_clusters_plan");
+  unsigned long long host_stat[CLU_WORDS];
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // (both refusals before the next launch: the stream is idle here, so the arena may go back as it is)
+  const u64 count = host_stat[CLU_LARGE];
+  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "chains: more anchors than hits"); }
+  // the groups in LDS: the two launch shapes of the clusters, each launch with the LDS of its largest group
+  {
+    const u64 most = host_stat[CLU_MAX_SMALL];
+    if(most > cap) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "chains: a group in LDS above the capacity"); }
+    u32 fit = CLU_CAP_MIN;
+    while(fit < most && fit < CLU_WAVE_MAX) { fit *= 2; }
+    const u64 narrow = std::min<u64>(fit, cap);                 // the groups of up to this many anchors
+    size_t lds = size_t(fit) * CLU_LDS_BYTES;
+    u64 per_cu = std::max<u64>(1, std::min<u64>(32, (160u << 10) / (lds + 2048)));
+    hipLaunchKernelGGL((k_chains_lds<64>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(64), lds, st, goff, n_groups,
+                       recs, hoff, hits, info, map, P, fit, u64(0), narrow, job.top, members, job.summaries, stat);
+    LAUNCH_CHECK("k_chains_lds");
+    if(most > narrow)
+    {
+      while(fit < most) { fit *= 2; }
+      lds = size_t(fit) * CLU_LDS_BYTES;
+      if(lds > (48u << 10))
+      {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chains_lds<TPB>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+      }
+      per_cu = std::max<u64>(1, std::min<u64>(8, (160u << 10) / (lds + 2048)));
+      hipLaunchKernelGGL((k_chains_lds<TPB>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(TPB), lds, st, goff, n_groups,
+                         recs, hoff, hits, info, map, P, fit, narrow, u64(cap), job.top, members, job.summaries, stat);
+      LAUNCH_CHECK("k_chains_lds");
+    }
+  }
+  // the groups above the capacity
+  if(count > 0)
+  {
+    u64 *loff = nullptr, *xs = nullptr, *pes = nullptr, *gk = nullptr, *ka = nullptr, *kb = nullptr, *sx = nullptr, *spe = nullptr, *sgk = nullptr;
+    u32 *pa = nullptr, *pb = nullptr, *prd = nullptr, *mrk = nullptr;
+    char* tmp = nullptr;
+    HIP_TRY(scratch.get(loff, n_groups + 1));
+    HIP_TRY(scratch.get(xs, count)); HIP_TRY(scratch.get(pes, count)); HIP_TRY(scratch.get(gk, count));
+    HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
+    HIP_TRY(scratch.get(sx, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
+    HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count)); HIP_TRY(scratch.get(prd, count)); HIP_TRY(scratch.get(mrk, count));
+    size_t bytes = 0, need = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, lsize, loff, size_t(n_groups + 1), st)); bytes = std::max(bytes, need);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, xs, ka, pa, pb, size_t(count), 0, 64, st)); bytes = std::max(bytes, need);
+    HIP_TRY(scratch.get(tmp, bytes));
+    const dim3 lanes(grid_for(count));
+    HIP_TRY(hipMemsetAsync(lsize + n_groups, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(mrk, 0xFF, count * sizeof(u32), st));                                                           // CHN_NO: no anchor is used
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, lsize, loff, size_t(n_groups + 1), st));
+    hipLaunchKernelGGL(k_chains_large_gather, lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, xs, pes, gk, pa);
+    LAUNCH_CHECK("k_chains_large_gather");
+    // by (group, unplaced, x, q, l): q << 32 | qe first, then stable sorts by x and by the group word
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, pes, ka, pa, pb, size_t(count), 0, 64, st));                     // pb: by (q, l)
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, xs, pb, count, ka);
+    LAUNCH_CHECK("k_clusters_large_take");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, kb, pb, pa, size_t(count), 0, 64, st));                      // pa: by (x, q, l)
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, gk, pa, count, ka);
+    LAUNCH_CHECK("k_clusters_large_take");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, sgk, pa, pb, size_t(count), 0, 34, st));                     // sgk, pb: by (group, x, q, l)
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, xs, pb, count, sx);
+    LAUNCH_CHECK("k_clusters_large_take");
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, pes, pb, count, spe);
+    LAUNCH_CHECK("k_clusters_large_take");
+    // f and pred, then the order of the visit: by (group, f descending, place), two stable sorts again
+    const dim3 grid(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * 8)));
+    hipLaunchKernelGGL(k_chains_large_dp, grid, dim3(64), 0, st, loff, lsize, n_groups, sx, spe, sgk, P, ka, prd, pa);
+    LAUNCH_CHECK("k_chains_large_dp");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, kb, pa, pb, size_t(count), 0, 51, st));                      // pb: by f descending
+    hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, sgk, pb, count, ka);
+    LAUNCH_CHECK("k_clusters_large_take");
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, kb, pb, pa, size_t(count), 0, 34, st));                      // pa: the order of the visit
+    hipLaunchKernelGGL(k_chains_large_finish, grid, dim3(TPB), 0, st, loff, lsize, n_groups, sx, spe, sgk, prd, mrk, pa, P, job.top, members, job.summaries,
+                       stat);
+    LAUNCH_CHECK("k_chains_large_finish");
+  }
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  out->invalid_groups = host_stat[CLU_INVALID]; out->seeds = host_stat[CLU_SEEDS]; out->anchors = host_stat[CLU_ANCHORS];
+  out->unplaced = host_stat[CLU_UNPLACED]; out->chains = host_stat[CLU_CLUSTERS]; out->spilled = host_stat[CLU_SPILLED];
+  return GCSA2_OK;
+}
+
+// The fused chain forms: fused_hits, then the chain core with the seed offsets as the groups.
+int fused_chains_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
+                      u64 w, u64 hash_seed, u64 hit_max, int over, const ChainsJob& job, gcsa2_chain_stats* out, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  FusedHits f;
+  const int rc = fused_hits(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over,
+                            (minimizers ? "minimizer_chains" : "kmer_chains"), "chains", f, st);
+  if(rc != GCSA2_OK) { return rc; }
+  return chains_core(ix, f.seed_off, n_patterns, f.seeds, f.m, f.hit_off, f.hit_values, f.h, job, out, scratch, st);
+}
+
+int fused_chains_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
+                       u64 hash_seed, u64 hit_max, int over, const ChainsJob& job, const char* name, gcsa2_chain_stats* stats, void* stream)
+{
+  u64 unused_seeds = 0, unused_hits = 0;
+  int rc = chains_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.params, "d_coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  rc = chains_member_check(job.params, n_patterns);
+  if(rc != GCSA2_OK) { return rc; }
+  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
+  gcsa2_chain_stats pre{};
+  pre.groups = n_patterns;
+  return stats_entry(name, ix, stats, pre, n_patterns == 0, [&](gcsa2_chain_stats& sums) -> int
+  {
+    return fused_chains_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
+  });
+}
+
+// Both host forms, as clusters_batch: the coordinate map goes to the device once; each piece is one fused device call on its
+// thread's stream into device rows, member rows and summaries of its own, copied to the piece's place in the caller's arrays.
+int chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
+                 u64 hash_seed, u64 hit_max, int over, u64 shift, const uint64_t* coord_of_bin, u64 n_bins, const gcsa2_chain_params* params, gcsa2_chain* top,
+                 gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries, gcsa2_chain_stats* stats, const char* name)
+{
+  u64 unused_seeds = 0, unused_hits = 0;
+  int rc = chains_checks(ix, shift, coord_of_bin, n_bins, params, "coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  rc = chains_member_check(params, n_patterns);
+  if(rc != GCSA2_OK) { return rc; }
+  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
+  gcsa2_chain_stats sums{};
+  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
+  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": offsets is NULL"); }
+  rc = reads_ok(patterns, offsets, n_patterns, name);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  if(host_windows(offsets, n_patterns, k, (minimizers ? 1 : stride)) >= (u64(1) << 32))
+  {
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch");
+  }
+  DeviceGuard guard(ix->device);
+  DBuf<u64> d_map;
+  HIP_TRY(d_map.alloc(n_bins));
+  HIP_TRY(hipMemcpy(d_map.p, coord_of_bin, n_bins * sizeof(u64), hipMemcpyHostToDevice));
+  const u64 top_n = params->top_n, per_read = (members != nullptr ? top_n * params->member_cap : 0);      // member entries of a read
+  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  std::vector<gcsa2_chain_stats> done(cut.size() - 1);
+  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
+  {
+    DBuf<u8> d_pat; DBuf<u64> d_off; DBuf<gcsa2_chain> d_top; DBuf<gcsa2_chain_anchor> d_mem; DBuf<gcsa2_chain_summary> d_sum;
+    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
+    hipError_t e = (top != nullptr ? d_top.alloc(p.count * top_n) : hipSuccess);
+    if(e == hipSuccess && per_read > 0) { e = d_mem.alloc(p.count * per_read); }
+    if(e == hipSuccess && summaries != nullptr) { e = d_sum.alloc(p.count); }
+    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
+    const int piece_rc = (minimizers ? gcsa2_minimizer_chains_device(ix, d_pat.p, d_off.p, p.count, k, w, hash_seed, hit_max, over, shift, d_map.p, n_bins, params,
+                                                                      d_top.p, d_mem.p, d_sum.p, &done[p.c], p.stream)
+                                     : gcsa2_kmer_chains_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, over, shift, d_map.p, n_bins, params,
+                                                                 d_top.p, d_mem.p, d_sum.p, &done[p.c], p.stream));
+    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
+    if(top != nullptr) { e = hipMemcpy(top + p.b * top_n, d_top.p, p.count * top_n * sizeof(gcsa2_chain), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && per_read > 0) { e = hipMemcpy(members + p.b * per_read, d_mem.p, p.count * per_read * sizeof(gcsa2_chain_anchor), hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && summaries != nullptr) { e = hipMemcpy(summaries + p.b, d_sum.p, p.count * sizeof(gcsa2_chain_summary), hipMemcpyDeviceToHost); }
+    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
+    return true;
+  });
+  if(rc != GCSA2_OK) { return rc; }
+  for(const gcsa2_chain_stats& s : done) { sum_stats(sums, s); }
+  if(stats != nullptr) { *stats = sums; }
+  return GCSA2_OK;
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_seed_chains_device(const gcsa2_index* ix, const uint64_t* d_group_offsets, uint64_t n_groups, const gcsa2_mem* d_seeds, uint64_t n_seeds,
+                             const uint64_t* d_hit_offsets, const uint64_t* d_hits, uint64_t n_hits, uint64_t shift, const uint64_t* d_coord_of_bin,
+                             uint64_t n_bins, const gcsa2_chain_params* params, gcsa2_chain* d_top, gcsa2_chain_anchor* d_members,
+                             gcsa2_chain_summary* d_summaries, gcsa2_chain_stats* stats, void* stream)
+{
+  int rc = chains_checks(ix, shift, d_coord_of_bin, n_bins, params, "d_coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_group_offsets is NULL"); }
+  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_seeds is NULL"); }
+  if(n_seeds > 0 && d_hit_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_hit_offsets is NULL"); }
+  if(n_hits > 0 && d_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_hits is NULL"); }
+  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more groups in one call; split the batch"); }
+  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more seeds in one call; split the batch"); }
+  if(n_hits >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more hits in one call; split the batch"); }
+  rc = chains_member_check(params, n_groups);
+  if(rc != GCSA2_OK) { return rc; }
+  gcsa2_chain_stats pre{};
+  pre.groups = n_groups;
+  return stats_entry("seed_chains", ix, stats, pre, n_groups == 0, [&](gcsa2_chain_stats& sums) -> int
+  {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scratch scratch(ix, st);
+    const ChainsJob job{shift, d_coord_of_bin, n_bins, params, d_top, d_members, d_summaries};
+    return chains_core(ix, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, job, &sums, scratch, st);
+  });
+}
+
+int gcsa2_kmer_chains_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
+                             uint64_t hit_max, int over, uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins, const gcsa2_chain_params* params,
+                             gcsa2_chain* d_top, gcsa2_chain_anchor* d_members, gcsa2_chain_summary* d_summaries, gcsa2_chain_stats* stats, void* stream)
+{
+  const ChainsJob job{shift, d_coord_of_bin, n_bins, params, d_top, d_members, d_summaries};
+  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, job, "kmer_chains", stats, stream);
+}
+
+int gcsa2_minimizer_chains_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                  uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins,
+                                  const gcsa2_chain_params* params, gcsa2_chain* d_top, gcsa2_chain_anchor* d_members, gcsa2_chain_summary* d_summaries,
+                                  gcsa2_chain_stats* stats, void* stream)
+{
+  const ChainsJob job{shift, d_coord_of_bin, n_bins, params, d_top, d_members, d_summaries};
+  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, job, "minimizer_chains", stats, stream);
+}
+
+int gcsa2_kmer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
+                            uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, const gcsa2_chain_params* params,
+                            gcsa2_chain* top, gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries, gcsa2_chain_stats* stats)
+{
+  return chains_batch(ix, patterns, offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, shift, coord_of_bin, n_bins, params, top, members, summaries, stats,
+                      "gcsa2_kmer_chains_batch");
+}
+
+int gcsa2_minimizer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                 uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins,
+                                 const gcsa2_chain_params* params, gcsa2_chain* top, gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries,
+                                 gcsa2_chain_stats* stats)
+{
+  return chains_batch(ix, patterns, offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, shift, coord_of_bin, n_bins, params, top, members, summaries, stats,
+                      "gcsa2_minimizer_chains_batch");
 }
 
 }  // extern "C"

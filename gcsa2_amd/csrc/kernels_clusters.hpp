@@ -120,6 +120,17 @@ __global__ __launch_bounds__(TPB) void k_clusters_plan(const u64* __restrict__ g
 // without a cluster holds (0, CLU_NONE): a cluster has at least one anchor, so its score is not 0.
 __device__ __forceinline__ bool clu_ahead(u64 sa, u64 da, u64 sb, u64 db) { return sa > sb || (sa == sb && da < db); }
 
+// One wavefront holds a top row sorted by clu_ahead in its registers, lane j the j-th entry (score, key, payload): the entry
+// (ns, nk, nx), the same in every lane, goes to its place and the entries behind it move down one lane; the last falls off.
+__device__ __forceinline__ void clu_top_insert(u64& rs, u64& rk, u64& rx, u64 ns, u64 nk, u64 nx)
+{
+  const u32 lane = threadIdx.x & 63;
+  const u32 at = u32(__popcll(__ballot(clu_ahead(rs, rk, ns, nk))));             // the row is sorted: those ahead are a prefix
+  const u64 us = __shfl_up(rs, 1, 64), uk = __shfl_up(rk, 1, 64), ux = __shfl_up(rx, 1, 64);
+  if(lane == at) { rs = ns; rk = nk; rx = nx; }
+  else if(lane > at) { rs = us; rk = uk; rx = ux; }
+}
+
 struct CluShared
 {
   u64 wave[TPB / 64];
@@ -186,11 +197,7 @@ __device__ u64 clu_score(const View& view, u64 begin, u64 end, u64 anchors_all, 
       {
         const int src = __ffsll((unsigned long long)fresh) - 1;
         fresh &= fresh - 1;
-        const u64 ns = __shfl(s, src, 64), nk = __shfl(k, src, 64), nx = __shfl(x, src, 64);
-        const u32 at = u32(__popcll(__ballot(clu_ahead(rs, rk, ns, nk))));       // the row is sorted: those ahead are a prefix
-        const u64 us = __shfl_up(rs, 1, 64), uk = __shfl_up(rk, 1, 64), ux = __shfl_up(rx, 1, 64);
-        if(lane == at) { rs = ns; rk = nk; rx = nx; }
-        else if(lane > at) { rs = us; rk = uk; rx = ux; }
+        clu_top_insert(rs, rk, rx, __shfl(s, src, 64), __shfl(k, src, 64), __shfl(x, src, 64));
       }
     }
     sh.win_score[lane] = rs; sh.win_key[lane] = rk; sh.win_at[lane] = rx;
@@ -435,13 +442,8 @@ __global__ __launch_bounds__(TPB) void k_clusters_large_gather(const u64* __rest
 {
   const u64 e = u64(blockIdx.x) * TPB + threadIdx.x;
   if(e >= count) { return; }
-  u64 lo = 0, hi = n_groups;                                 // the last g with loff[g] <= e: loff[0] = 0, loff[n_groups] = count > e
-  while(hi - lo > 1)
-  {
-    const u64 mid = lo + (hi - lo) / 2;
-    if(loff[mid] <= e) { lo = mid; } else { hi = mid; }
-  }
-  const u64 g = lo, first = goff[g], last = goff[g + 1], h = hoff[first] + (e - loff[g]), i = clu_seed_of(hoff, first, last, h);
+  // the last g with loff[g] <= e: loff[0] = 0, loff[n_groups] = count > e (the search of clu_seed_of over the group sizes)
+  const u64 g = clu_seed_of(loff, 0, n_groups, e), first = goff[g], last = goff[g + 1], h = hoff[first] + (e - loff[g]), i = clu_seed_of(hoff, first, last, h);
   u64 key = CLU_NONE, p = CLU_NONE;
   const bool placed = clu_place(map, hits[h], seeds[5 * i], seeds[5 * i + 1], key, p);
   dk[e] = (placed ? key : CLU_NONE); pe[e] = (placed ? p : CLU_NONE); gk[e] = (g << 1) | (placed ? 0 : 1);

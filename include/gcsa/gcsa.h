@@ -13,9 +13,17 @@
 
 #include "files.h"
 #include "support.h"
+#include "../gcsa2_hip_chains.h"
 
 namespace gcsa
 {
+
+// The parameters of the seed-chain calls (gcsa2_chain_params), with the defaults of the Python binding.
+struct ChainParameters
+{
+  size_type band = 64, max_gap = 5000, lookback = 16, match = 1, gap = 1, min_score = 0, top_n = 5, member_cap = 0;
+  gcsa2_chain_params c() const { return gcsa2_chain_params{band, max_gap, lookback, match, gap, min_score, top_n, member_cap}; }
+};
 
 class GCSA
 {
@@ -537,6 +545,62 @@ public:
     check(rc, "GCSA::seed_clusters_device()");
   }
 
+  // Seed chains (gcsa2_kmer_chains_batch): per read the top_n (1 .. GCSA2_CHAIN_TOP_LIMIT) colinear chains of the hits of its
+  // k-mers -- larger score first, then more anchors, then the smaller place of the end; all zero behind the last chain --, of
+  // every chain its first member_cap anchors from its end backwards, and {anchors, unplaced, chains}.  coord_of_bin as for the
+  // clusters.  top (reads x top_n), members (reads x top_n x member_cap; empty with member_cap == 0) and summaries (one per
+  // read) are resized and WRITTEN.  Needs no LCP array.
+  void kmer_chains_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type stride,
+                         size_type hit_max, bool sample, size_type shift, const std::vector<size_type>& coord_of_bin, const ChainParameters& parameters,
+                         std::vector<gcsa2_chain>& top, std::vector<gcsa2_chain_anchor>& members, std::vector<gcsa2_chain_summary>& summaries,
+                         gcsa2_chain_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    const gcsa2_chain_params params = parameters.c();
+    this->chain_outputs(np, params, top, members, summaries);
+    const int rc = gcsa2_kmer_chains_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                           k, stride, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, shift,
+                                           coord_of_bin.empty() ? nullptr : coord_of_bin.data(), coord_of_bin.size(), &params,
+                                           top.empty() ? nullptr : top.data(), members.empty() ? nullptr : members.data(),
+                                           summaries.empty() ? nullptr : summaries.data(), stats);
+    check(rc, "GCSA::kmer_chains_batch()");
+  }
+
+  // The same over the (w, k)-minimizers of every read (gcsa2_minimizer_chains_batch).
+  void minimizer_chains_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                              size_type hash_seed, size_type hit_max, bool sample, size_type shift, const std::vector<size_type>& coord_of_bin,
+                              const ChainParameters& parameters, std::vector<gcsa2_chain>& top, std::vector<gcsa2_chain_anchor>& members,
+                              std::vector<gcsa2_chain_summary>& summaries, gcsa2_chain_stats* stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    const gcsa2_chain_params params = parameters.c();
+    this->chain_outputs(np, params, top, members, summaries);
+    const int rc = gcsa2_minimizer_chains_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                                k, w, hash_seed, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, shift,
+                                                coord_of_bin.empty() ? nullptr : coord_of_bin.data(), coord_of_bin.size(), &params,
+                                                top.empty() ? nullptr : top.data(), members.empty() ? nullptr : members.data(),
+                                                summaries.empty() ? nullptr : summaries.data(), stats);
+    check(rc, "GCSA::minimizer_chains_batch()");
+  }
+
+  // The chains of a seed CSR that is already in device memory with its hit offsets and hits (gcsa2_seed_chains_device): raw
+  // device pointers; d_top, d_members and d_summaries may be null.
+  void seed_chains_device(const size_type* d_group_offsets, size_type n_groups, const gcsa2_mem* d_seeds, size_type n_seeds,
+                          const size_type* d_hit_offsets, const node_type* d_hits, size_type n_hits, size_type shift,
+                          const size_type* d_coord_of_bin, size_type n_bins, const ChainParameters& parameters, gcsa2_chain* d_top,
+                          gcsa2_chain_anchor* d_members, gcsa2_chain_summary* d_summaries, gcsa2_chain_stats* stats = nullptr,
+                          void* stream = nullptr) const
+  {
+    const gcsa2_chain_params params = parameters.c();
+    const int rc = gcsa2_seed_chains_device(handle, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, shift, d_coord_of_bin,
+                                            n_bins, &params, d_top, d_members, d_summaries, stats, stream);
+    check(rc, "GCSA::seed_chains_device()");
+  }
+
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least
   // reseed_length bases, the matches of at least min_length that occur more often than the MEM, with their hits by the rules of
   // mem_hits_batch.  Sub-MEMs of MEM k: [sub_offsets[k], sub_offsets[k + 1]); hits of sub-MEM i: [hit_offsets[i], hit_offsets[i + 1]).
@@ -734,6 +798,16 @@ private:
     check(gcsa2_lf_all_batch(handle, in, 1, all, out.data()), "GCSA::LF_all()");
     size_type limit = all ? alpha.sigma - 2 : alpha.fast_chars;
     for(size_type c = 1; c <= limit && c < results.size(); c++) { results[c] = range_type(out[2 * c], out[2 * c + 1]); }
+  }
+  // the outputs of a chains call for np reads, zeroed; nothing for parameters that the call will refuse
+  static void chain_outputs(size_type np, const gcsa2_chain_params& p, std::vector<gcsa2_chain>& top, std::vector<gcsa2_chain_anchor>& members,
+                            std::vector<gcsa2_chain_summary>& summaries)
+  {
+    const size_type rows = np * (p.top_n <= GCSA2_CHAIN_TOP_LIMIT ? p.top_n : 0);
+    const bool fits = (p.member_cap == 0 || rows == 0 || p.member_cap <= 0xFFFFFFFFull / rows);
+    top.assign(rows, gcsa2_chain{0, 0, 0, 0, 0, 0, 0, 0});
+    members.assign(fits ? rows * p.member_cap : 0, gcsa2_chain_anchor{0, 0, 0});
+    summaries.assign(np, gcsa2_chain_summary{0, 0, 0});
   }
   std::vector<size_type> sample_info(size_type node) const
   {

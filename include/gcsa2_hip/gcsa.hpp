@@ -8,6 +8,7 @@
 #ifndef GCSA2_HIP_GCSA_HPP
 #define GCSA2_HIP_GCSA_HPP
 
+#include "../gcsa2_hip_chains.h"
 #include "../gcsa/utils.h"
 #include "../gcsa/files.h"
 #include "../gcsa/support.h"
