@@ -6229,6 +6229,9 @@ int gcsa2_seed_top_classes_device(const gcsa2_index* ix, const uint64_t* d_group
 
 }  // extern "C"
 
+// ==== groups of placed anchors: the plan, the launch shapes and the entry points that seed clusters and seed chains share ====
+#include "host_anchors.hpp"
+
 // ==== seed clusters: per read (or group of seed records) the top diagonal bands of its anchors (kernels_clusters.hpp) ====
 namespace {
 
@@ -6253,19 +6256,9 @@ int clusters_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, 
   return GCSA2_OK;
 }
 
-// GCSA2_CLUSTER_LDS, and GCSA2_CHAIN_LDS for the chain calls (test knobs, read per call): the anchors of a group that
-// k_clusters_lds (k_chains_lds) holds, a power of two from CLU_CAP_MIN to CLU_CAP_DEFAULT; anything else is ignored.  No result
-// but stats.spilled depends on it.
-u32 cluster_capacity(const char* knob = "GCSA2_CLUSTER_LDS")
-{
-  u64 v = 0;
-  if(env_count(knob, &v) && v >= CLU_CAP_MIN && v <= CLU_CAP_DEFAULT && (v & (v - 1)) == 0) { return u32(v); }
-  return CLU_CAP_DEFAULT;
-}
-
 // The cluster core.  n_groups >= 1; n_groups, n_seeds, n_hits < 2^32.  Writes every row and summary and fills every field of
-// *out but `groups`.  One host round trip (the plan's counters: the largest group in LDS sizes the launch, the anchors above
-// the capacity size the large path), then the end.  Scratch: 16 bytes per group; for the large path 8 bytes per group and 92
+// *out but `groups`.  One host round trip (anchors_plan: the largest group in LDS sizes the launch, the anchors above the
+// capacity size the large path), then the end.  Scratch: 16 bytes per group; for the large path 8 bytes per group and 92
 // bytes per anchor of a group above the capacity, and hipCUB's.
 int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa2_mem* seeds, u64 n_seeds, const u64* hoff, const u64* hits, u64 n_hits,
                   const ClustersJob& job, gcsa2_cluster_stats* out, Scratch& scratch, hipStream_t st)
@@ -6273,75 +6266,43 @@ int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gc
   static_assert(sizeof(gcsa2_mem) == 5 * sizeof(u64), "gcsa2_mem is five words");
   const u64* recs = reinterpret_cast<const u64*>(seeds);
   const CluMap map{u32(job.shift), job.coord_of_bin, job.n_bins};
-  const u32 cap = cluster_capacity(), top_n = u32(job.top_n);
-  unsigned long long* stat = nullptr;
-  u64 *info = nullptr, *lsize = nullptr;
-  HIP_TRY(scratch.get(stat, CLU_WORDS));
-  HIP_TRY(scratch.get(info, n_groups));
-  HIP_TRY(scratch.get(lsize, n_groups + 1));
-  HIP_TRY(hipMemsetAsync(stat, 0, CLU_WORDS * sizeof(unsigned long long), st));
-  scratch.settled = false;
-  const u64 resident = u64(ix->compute_units) * 8;
-  hipLaunchKernelGGL(k_clusters_plan, dim3(unsigned(std::min<u64>((n_groups + 3) / 4, resident))), dim3(TPB), 0, st, goff, n_groups, n_seeds, hoff, n_hits,
-                     u64(cap), info, lsize, stat);
-  LAUNCH_CHECK("k_clusters_plan");
-  unsigned long long host_stat[CLU_WORDS];
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  // (both refusals before the next launch: the stream is idle here, so the arena may go back as it is)
-  const u64 count = host_stat[CLU_LARGE];
-  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: more anchors than hits"); }
-  // the groups in LDS: one wavefront each up to CLU_WAVE_MAX anchors, a workgroup of 256 lanes each above; a launch takes the
-  // LDS of its largest group
+  const u32 cap = cluster_capacity("GCSA2_CLUSTER_LDS"), top_n = u32(job.top_n);
+  AnchorPlan plan;
+  int rc = anchors_plan(ix, goff, n_groups, n_seeds, hoff, n_hits, cap, "clusters", plan, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  rc = anchors_lds_launches(ix, n_groups, plan.most, cap, reinterpret_cast<const void*>(&k_clusters_lds<TPB>), "k_clusters_lds",
+                            [&](auto width, dim3 grid, size_t lds, u32 fit, u64 above, u64 spill)
   {
-    const u64 most = host_stat[CLU_MAX_SMALL];
-    if(most > cap) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "clusters: a group in LDS above the capacity"); }
-    u32 fit = CLU_CAP_MIN;
-    while(fit < most && fit < CLU_WAVE_MAX) { fit *= 2; }
-    const u64 narrow = std::min<u64>(fit, cap);                 // the groups of up to this many anchors
-    size_t lds = size_t(fit) * CLU_LDS_BYTES;
-    u64 per_cu = std::max<u64>(1, std::min<u64>(32, (160u << 10) / (lds + 2048)));
-    hipLaunchKernelGGL((k_clusters_lds<64>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(64), lds, st, goff, n_groups,
-                       recs, hoff, hits, info, map, job.band, top_n, fit, u64(0), narrow, job.top, job.summaries, stat);
-    LAUNCH_CHECK("k_clusters_lds");
-    if(most > narrow)
-    {
-      while(fit < most) { fit *= 2; }
-      lds = size_t(fit) * CLU_LDS_BYTES;
-      if(lds > (48u << 10))
-      {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_clusters_lds<TPB>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-      }
-      per_cu = std::max<u64>(1, std::min<u64>(8, (160u << 10) / (lds + 2048)));
-      hipLaunchKernelGGL((k_clusters_lds<TPB>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(TPB), lds, st, goff, n_groups,
-                         recs, hoff, hits, info, map, job.band, top_n, fit, narrow, u64(cap), job.top, job.summaries, stat);
-      LAUNCH_CHECK("k_clusters_lds");
-    }
-  }
+    constexpr u32 T = decltype(width)::value;
+    hipLaunchKernelGGL((k_clusters_lds<T>), grid, dim3(T), lds, st, goff, n_groups, recs, hoff, hits, plan.info, map, job.band, top_n, fit, above, spill, job.top,
+                       job.summaries, plan.stat);
+  });
+  if(rc != GCSA2_OK) { return rc; }
   // the groups above the capacity
-  if(count > 0)
+  if(const u64 count = plan.count)
   {
     u64 *loff = nullptr, *dk = nullptr, *pe = nullptr, *gk = nullptr, *ka = nullptr, *kb = nullptr, *sdk = nullptr, *spe = nullptr, *sgk = nullptr;
     u64 *key2 = nullptr, *ends = nullptr, *reach = nullptr;
     u32 *pa = nullptr, *pb = nullptr;
     char* tmp = nullptr;
-    HIP_TRY(scratch.get(loff, n_groups + 1));
-    HIP_TRY(scratch.get(dk, count)); HIP_TRY(scratch.get(pe, count)); HIP_TRY(scratch.get(gk, count));
-    HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
-    HIP_TRY(scratch.get(sdk, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
-    HIP_TRY(scratch.get(key2, count)); HIP_TRY(scratch.get(ends, count)); HIP_TRY(scratch.get(reach, count));
-    HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count));
-    size_t bytes = 0, need = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, lsize, loff, size_t(n_groups + 1), st)); bytes = std::max(bytes, need);
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, ka, pa, pb, size_t(count), 0, 64, st)); bytes = std::max(bytes, need);
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, ka, kb, hipcub::Max(), size_t(count), st)); bytes = std::max(bytes, need);
-    HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, ka, kb, size_t(count), st)); bytes = std::max(bytes, need);
-    HIP_TRY(scratch.get(tmp, bytes));
+    size_t bytes = 0;
+    rc = anchors_large_offsets(plan, n_groups, loff, tmp, bytes, scratch, st, [&](size_t& most) -> int
+    {
+      HIP_TRY(scratch.get(dk, count)); HIP_TRY(scratch.get(pe, count)); HIP_TRY(scratch.get(gk, count));
+      HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
+      HIP_TRY(scratch.get(sdk, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
+      HIP_TRY(scratch.get(key2, count)); HIP_TRY(scratch.get(ends, count)); HIP_TRY(scratch.get(reach, count));
+      HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count));
+      size_t need = 0;
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, dk, ka, pa, pb, size_t(count), 0, 64, st)); most = std::max(most, need);
+      HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, ka, kb, hipcub::Max(), size_t(count), st)); most = std::max(most, need);
+      HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, need, ka, kb, size_t(count), st)); most = std::max(most, need);
+      return GCSA2_OK;
+    });
+    if(rc != GCSA2_OK) { return rc; }
     const dim3 lanes(grid_for(count));
-    HIP_TRY(hipMemsetAsync(lsize + n_groups, 0, sizeof(u64), st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, lsize, loff, size_t(n_groups + 1), st));
-    hipLaunchKernelGGL(k_clusters_large_gather, lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, dk, pe, gk, pa);
-    LAUNCH_CHECK("k_clusters_large_gather");
+    hipLaunchKernelGGL((k_anchors_large_gather<clu_place>), lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, dk, pe, gk, pa);
+    LAUNCH_CHECK("k_anchors_large_gather");
     // by (group, unplaced, diagonal): the diagonal first, then a stable sort by the group word
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, dk, ka, pa, pb, size_t(count), 0, 64, st));                     // pb: by diagonal
     hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, gk, pb, count, ka);
@@ -6366,140 +6327,37 @@ int clusters_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gc
     LAUNCH_CHECK("k_clusters_large_cover");
     HIP_TRY(hipcub::DeviceScan::InclusiveSum(tmp, bytes, ka, kb, size_t(count), st));
     const dim3 grid(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * 8)));
-    hipLaunchKernelGGL(k_clusters_large_score, grid, dim3(TPB), 0, st, loff, lsize, n_groups, sdk, spe, sgk, key2, kb, top_n, job.top, job.summaries, stat);
+    hipLaunchKernelGGL(k_clusters_large_score, grid, dim3(TPB), 0, st, loff, plan.lsize, n_groups, sdk, spe, sgk, key2, kb, top_n, job.top, job.summaries, plan.stat);
     LAUNCH_CHECK("k_clusters_large_score");
   }
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  out->invalid_groups = host_stat[CLU_INVALID]; out->seeds = host_stat[CLU_SEEDS]; out->anchors = host_stat[CLU_ANCHORS];
-  out->unplaced = host_stat[CLU_UNPLACED]; out->clusters = host_stat[CLU_CLUSTERS]; out->spilled = host_stat[CLU_SPILLED];
-  return GCSA2_OK;
+  return anchors_tail(plan, out, &gcsa2_cluster_stats::clusters, scratch, st);
 }
 
-// What the fused cluster and chain forms run first, after their argument checks (0 < n_patterns < 2^32): the windows (every
-// stride-th, or the minimizers) and the hits call's own core behind them (kmer_hits_found) into scratch of this call.  The hit
-// buffer is sized by a guess -- four hits per window, no more than hit_max allows -- and a batch beyond it runs the hits again
-// with the size the first run reported.  `name` is the call's ("kmer_clusters"), `what` heads the refusal of 2^32 seeds or hits.
-struct FusedHits { u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0; gcsa2_mem* seeds = nullptr; };
-
-int fused_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
-               u64 w, u64 hash_seed, u64 hit_max, int over, const char* name, const char* what, FusedHits& out, hipStream_t st)
+// the fused cluster forms
+int fused_clusters_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, const AnchorWindows& win,
+                         const ClustersJob& job, const char* name, gcsa2_cluster_stats* stats, void* stream)
 {
-  u64 *woff = nullptr, total = 0;
-  gcsa2_minimizer* mins = nullptr;
-  int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, name, st,
-                                          woff, mins, total)
-                       : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, name, st, woff, total));
-  if(rc != GCSA2_OK) { return rc; }
-  u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0;
-  gcsa2_mem* seeds = nullptr;
-  u64 room = std::max<u64>(4 * total, 1024);
-  if(hit_max > 0 && hit_max < 4) { room = std::max<u64>(hit_max * total, 1); }
-  HIP_TRY(scratch.get(seed_off, n_patterns + 1));
-  HIP_TRY(scratch.get(seeds, total));
-  HIP_TRY(scratch.get(hit_off, total + 1));
-  HIP_TRY(scratch.get(hit_values, room));
-  rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
-                       total, &m, hit_off, hit_values, room, &h, st);
-  if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && m <= total && h > room)
-  {
-    room = h;
-    HIP_TRY(scratch.get(hit_values, room));
-    g_error.clear();
-    rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
-                         total, &m, hit_off, hit_values, room, &h, st);
-  }
-  if(rc != GCSA2_OK) { return rc; }
-  if(m >= (u64(1) << 32) || h >= (u64(1) << 32))
-  {
-    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(what) + ": 2^32 or more seeds or hits in one call; split the batch");
-  }
-  out.seed_off = seed_off; out.seeds = seeds; out.hit_off = hit_off; out.hit_values = hit_values; out.m = m; out.h = h;
-  return GCSA2_OK;
+  return fused_anchors_entry(ix, d_patterns, d_offsets, n_patterns, win, job, name, "clusters",
+                             [&] { return clusters_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.top_n, "d_coord_of_bin"); }, clusters_core, stats, stream);
 }
 
-// The fused cluster forms: fused_hits, then the cluster core with the seed offsets as the groups.
-int fused_clusters_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
-                        u64 w, u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, gcsa2_cluster_stats* out, hipStream_t st)
+// both host forms: the top rows and the summaries of every piece
+int clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, const AnchorWindows& win, u64 shift,
+                   const uint64_t* coord_of_bin, u64 n_bins, u64 band, u64 top_n, gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats,
+                   const char* name)
 {
-  Scratch scratch(ix, st);
-  FusedHits f;
-  const int rc = fused_hits(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over,
-                            (minimizers ? "minimizer_clusters" : "kmer_clusters"), "clusters", f, st);
-  if(rc != GCSA2_OK) { return rc; }
-  return clusters_core(ix, f.seed_off, n_patterns, f.seeds, f.m, f.hit_off, f.hit_values, f.h, job, out, scratch, st);
-}
-
-int fused_clusters_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
-                         u64 hash_seed, u64 hit_max, int over, const ClustersJob& job, const char* name, gcsa2_cluster_stats* stats, void* stream)
-{
-  u64 unused_seeds = 0, unused_hits = 0;
-  int rc = clusters_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.top_n, "d_coord_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_cluster_stats pre{};
-  pre.groups = n_patterns;
-  return stats_entry(name, ix, stats, pre, n_patterns == 0, [&](gcsa2_cluster_stats& sums) -> int
+  const PieceOutput outs[] = {{top, top_n, sizeof(gcsa2_cluster)}, {summaries, 1, sizeof(gcsa2_cluster_summary)}};
+  return anchors_batch(ix, patterns, offsets, n_patterns, win, coord_of_bin, n_bins, outs, stats, name,
+                       [&] { return clusters_checks(ix, shift, coord_of_bin, n_bins, top_n, "coord_of_bin"); },
+                       [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, const u64* d_map, void* const* d, gcsa2_cluster_stats* done) -> int
   {
-    return fused_clusters_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
+    gcsa2_cluster* d_top = static_cast<gcsa2_cluster*>(d[0]);
+    gcsa2_cluster_summary* d_sum = static_cast<gcsa2_cluster_summary*>(d[1]);
+    return (win.minimizers ? gcsa2_minimizer_clusters_device(ix, d_pat, d_off, p.count, win.k, win.w, win.hash_seed, win.hit_max, win.over, shift, d_map, n_bins, band,
+                                                             top_n, d_top, d_sum, done, p.stream)
+                           : gcsa2_kmer_clusters_device(ix, d_pat, d_off, p.count, win.k, win.stride, win.hit_max, win.over, shift, d_map, n_bins, band, top_n, d_top,
+                                                        d_sum, done, p.stream));
   });
-}
-
-// Both host forms.  The coordinate map goes to the device once; each piece (for_read_pieces) is one fused device call on its
-// thread's stream into device rows and summaries of its own, copied to the piece's place in the caller's arrays.
-int clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
-                   u64 hash_seed, u64 hit_max, int over, u64 shift, const uint64_t* coord_of_bin, u64 n_bins, u64 band, u64 top_n, gcsa2_cluster* top,
-                   gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats, const char* name)
-{
-  u64 unused_seeds = 0, unused_hits = 0;
-  int rc = clusters_checks(ix, shift, coord_of_bin, n_bins, top_n, "coord_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_cluster_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": offsets is NULL"); }
-  rc = reads_ok(patterns, offsets, n_patterns, name);
-  if(rc != GCSA2_OK) { return rc; }
-  try {   // no C++ exception may cross the C boundary
-  g_error.clear();
-  if(host_windows(offsets, n_patterns, k, (minimizers ? 1 : stride)) >= (u64(1) << 32))
-  {
-    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch");
-  }
-  DeviceGuard guard(ix->device);
-  DBuf<u64> d_map;
-  HIP_TRY(d_map.alloc(n_bins));
-  HIP_TRY(hipMemcpy(d_map.p, coord_of_bin, n_bins * sizeof(u64), hipMemcpyHostToDevice));
-  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
-  std::vector<gcsa2_cluster_stats> done(cut.size() - 1);
-  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
-  {
-    DBuf<u8> d_pat; DBuf<u64> d_off; DBuf<gcsa2_cluster> d_top; DBuf<gcsa2_cluster_summary> d_sum;
-    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
-    hipError_t e = (top != nullptr ? d_top.alloc(p.count * top_n) : hipSuccess);
-    if(e == hipSuccess && summaries != nullptr) { e = d_sum.alloc(p.count); }
-    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
-    const int piece_rc = (minimizers ? gcsa2_minimizer_clusters_device(ix, d_pat.p, d_off.p, p.count, k, w, hash_seed, hit_max, over, shift, d_map.p, n_bins, band, top_n,
-                                                                        d_top.p, d_sum.p, &done[p.c], p.stream)
-                                     : gcsa2_kmer_clusters_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, over, shift, d_map.p, n_bins, band, top_n,
-                                                                   d_top.p, d_sum.p, &done[p.c], p.stream));
-    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
-    if(top != nullptr) { e = hipMemcpy(top + p.b * top_n, d_top.p, p.count * top_n * sizeof(gcsa2_cluster), hipMemcpyDeviceToHost); }
-    if(e == hipSuccess && summaries != nullptr) { e = hipMemcpy(summaries + p.b, d_sum.p, p.count * sizeof(gcsa2_cluster_summary), hipMemcpyDeviceToHost); }
-    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
-    return true;
-  });
-  if(rc != GCSA2_OK) { return rc; }
-  for(const gcsa2_cluster_stats& s : done) { sum_stats(sums, s); }
-  if(stats != nullptr) { *stats = sums; }
-  return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
 }
 
 }  // namespace
@@ -6513,13 +6371,8 @@ int gcsa2_seed_clusters_device(const gcsa2_index* ix, const uint64_t* d_group_of
 {
   int rc = clusters_checks(ix, shift, d_coord_of_bin, n_bins, top_n, "d_coord_of_bin");
   if(rc != GCSA2_OK) { return rc; }
-  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_group_offsets is NULL"); }
-  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_seeds is NULL"); }
-  if(n_seeds > 0 && d_hit_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_hit_offsets is NULL"); }
-  if(n_hits > 0 && d_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: d_hits is NULL"); }
-  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more groups in one call; split the batch"); }
-  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more seeds in one call; split the batch"); }
-  if(n_hits >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_clusters: 2^32 or more hits in one call; split the batch"); }
+  rc = seed_form_checks("seed_clusters", d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits);
+  if(rc != GCSA2_OK) { return rc; }
   gcsa2_cluster_stats pre{};
   pre.groups = n_groups;
   return stats_entry("seed_clusters", ix, stats, pre, n_groups == 0, [&](gcsa2_cluster_stats& sums) -> int
@@ -6536,7 +6389,7 @@ int gcsa2_kmer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patterns,
                                gcsa2_cluster* d_top, gcsa2_cluster_summary* d_summaries, gcsa2_cluster_stats* stats, void* stream)
 {
   const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
-  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, job, "kmer_clusters", stats, stream);
+  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, AnchorWindows{k, stride, false, 0, 0, hit_max, over}, job, "kmer_clusters", stats, stream);
 }
 
 int gcsa2_minimizer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
@@ -6545,23 +6398,23 @@ int gcsa2_minimizer_clusters_device(const gcsa2_index* ix, const uint8_t* d_patt
                                     void* stream)
 {
   const ClustersJob job{shift, d_coord_of_bin, n_bins, band, top_n, d_top, d_summaries};
-  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, job, "minimizer_clusters", stats, stream);
+  return fused_clusters_entry(ix, d_patterns, d_offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, job, "minimizer_clusters", stats, stream);
 }
 
 int gcsa2_kmer_clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
                               uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band, uint64_t top_n,
                               gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats)
 {
-  return clusters_batch(ix, patterns, offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, shift, coord_of_bin, n_bins, band, top_n, top, summaries, stats,
-                        "gcsa2_kmer_clusters_batch");
+  return clusters_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, stride, false, 0, 0, hit_max, over}, shift, coord_of_bin, n_bins, band, top_n, top,
+                        summaries, stats, "gcsa2_kmer_clusters_batch");
 }
 
 int gcsa2_minimizer_clusters_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
                                    uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, uint64_t band,
                                    uint64_t top_n, gcsa2_cluster* top, gcsa2_cluster_summary* summaries, gcsa2_cluster_stats* stats)
 {
-  return clusters_batch(ix, patterns, offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, shift, coord_of_bin, n_bins, band, top_n, top, summaries, stats,
-                        "gcsa2_minimizer_clusters_batch");
+  return clusters_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, shift, coord_of_bin, n_bins, band, top_n, top,
+                        summaries, stats, "gcsa2_minimizer_clusters_batch");
 }
 
 }  // extern "C"
@@ -6602,8 +6455,8 @@ int chains_member_check(const gcsa2_chain_params* p, u64 n_groups)
   return GCSA2_OK;
 }
 
-// The chain core, laid out as clusters_core.  n_groups >= 1; n_groups, n_seeds, n_hits < 2^32.  Writes every row, member row
-// and summary and fills every field of *out but `groups`.  One host round trip (the plan's counters), then the end.  Scratch:
+// The chain core, on the skeleton of clusters_core.  n_groups >= 1; n_groups, n_seeds, n_hits < 2^32.  Writes every row, member
+// row and summary and fills every field of *out but `groups`.  One host round trip (anchors_plan), then the end.  Scratch:
 // 16 bytes per group; for the large path 8 bytes per group and 80 bytes per anchor of a group above the capacity, and hipCUB's.
 int chains_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa2_mem* seeds, u64 n_seeds, const u64* hoff, const u64* hits, u64 n_hits,
                 const ChainsJob& job, gcsa2_chain_stats* out, Scratch& scratch, hipStream_t st)
@@ -6614,70 +6467,39 @@ int chains_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa
   const ChnParams P{p.band, p.max_gap, p.match, p.gap, p.min_score, p.member_cap, u32(p.lookback), u32(p.top_n)};
   gcsa2_chain_anchor* members = (p.member_cap > 0 ? job.members : nullptr);
   const u32 cap = cluster_capacity("GCSA2_CHAIN_LDS");
-  unsigned long long* stat = nullptr;
-  u64 *info = nullptr, *lsize = nullptr;
-  HIP_TRY(scratch.get(stat, CLU_WORDS));
-  HIP_TRY(scratch.get(info, n_groups));
-  HIP_TRY(scratch.get(lsize, n_groups + 1));
-  HIP_TRY(hipMemsetAsync(stat, 0, CLU_WORDS * sizeof(unsigned long long), st));
-  scratch.settled = false;
-  const u64 resident = u64(ix->compute_units) * 8;
-  hipLaunchKernelGGL(k_clusters_plan, dim3(unsigned(std::min<u64>((n_groups + 3) / 4, resident))), dim3(TPB), 0, st, goff, n_groups, n_seeds, hoff, n_hits,
-                     u64(cap), info, lsize, stat);
-  LAUNCH_CHECK("k_clusters_plan");
-  unsigned long long host_stat[CLU_WORDS];
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  // (both refusals before the next launch: the stream is idle here, so the arena may go back as it is)
-  const u64 count = host_stat[CLU_LARGE];
-  if(count >= (u64(1) << 32)) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "chains: more anchors than hits"); }
-  // the groups in LDS: the two launch shapes of the clusters, each launch with the LDS of its largest group
+  AnchorPlan plan;
+  int rc = anchors_plan(ix, goff, n_groups, n_seeds, hoff, n_hits, cap, "chains", plan, scratch, st);
+  if(rc != GCSA2_OK) { return rc; }
+  rc = anchors_lds_launches(ix, n_groups, plan.most, cap, reinterpret_cast<const void*>(&k_chains_lds<TPB>), "k_chains_lds",
+                            [&](auto width, dim3 grid, size_t lds, u32 fit, u64 above, u64 spill)
   {
-    const u64 most = host_stat[CLU_MAX_SMALL];
-    if(most > cap) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "chains: a group in LDS above the capacity"); }
-    u32 fit = CLU_CAP_MIN;
-    while(fit < most && fit < CLU_WAVE_MAX) { fit *= 2; }
-    const u64 narrow = std::min<u64>(fit, cap);                 // the groups of up to this many anchors
-    size_t lds = size_t(fit) * CLU_LDS_BYTES;
-    u64 per_cu = std::max<u64>(1, std::min<u64>(32, (160u << 10) / (lds + 2048)));
-    hipLaunchKernelGGL((k_chains_lds<64>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(64), lds, st, goff, n_groups,
-                       recs, hoff, hits, info, map, P, fit, u64(0), narrow, job.top, members, job.summaries, stat);
-    LAUNCH_CHECK("k_chains_lds");
-    if(most > narrow)
-    {
-      while(fit < most) { fit *= 2; }
-      lds = size_t(fit) * CLU_LDS_BYTES;
-      if(lds > (48u << 10))
-      {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chains_lds<TPB>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-      }
-      per_cu = std::max<u64>(1, std::min<u64>(8, (160u << 10) / (lds + 2048)));
-      hipLaunchKernelGGL((k_chains_lds<TPB>), dim3(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * per_cu * 4))), dim3(TPB), lds, st, goff, n_groups,
-                         recs, hoff, hits, info, map, P, fit, narrow, u64(cap), job.top, members, job.summaries, stat);
-      LAUNCH_CHECK("k_chains_lds");
-    }
-  }
+    constexpr u32 T = decltype(width)::value;
+    hipLaunchKernelGGL((k_chains_lds<T>), grid, dim3(T), lds, st, goff, n_groups, recs, hoff, hits, plan.info, map, P, fit, above, spill, job.top, members,
+                       job.summaries, plan.stat);
+  });
+  if(rc != GCSA2_OK) { return rc; }
   // the groups above the capacity
-  if(count > 0)
+  if(const u64 count = plan.count)
   {
     u64 *loff = nullptr, *xs = nullptr, *pes = nullptr, *gk = nullptr, *ka = nullptr, *kb = nullptr, *sx = nullptr, *spe = nullptr, *sgk = nullptr;
     u32 *pa = nullptr, *pb = nullptr, *prd = nullptr, *mrk = nullptr;
     char* tmp = nullptr;
-    HIP_TRY(scratch.get(loff, n_groups + 1));
-    HIP_TRY(scratch.get(xs, count)); HIP_TRY(scratch.get(pes, count)); HIP_TRY(scratch.get(gk, count));
-    HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
-    HIP_TRY(scratch.get(sx, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
-    HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count)); HIP_TRY(scratch.get(prd, count)); HIP_TRY(scratch.get(mrk, count));
-    size_t bytes = 0, need = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, lsize, loff, size_t(n_groups + 1), st)); bytes = std::max(bytes, need);
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, xs, ka, pa, pb, size_t(count), 0, 64, st)); bytes = std::max(bytes, need);
-    HIP_TRY(scratch.get(tmp, bytes));
+    size_t bytes = 0;
+    rc = anchors_large_offsets(plan, n_groups, loff, tmp, bytes, scratch, st, [&](size_t& most) -> int
+    {
+      HIP_TRY(scratch.get(xs, count)); HIP_TRY(scratch.get(pes, count)); HIP_TRY(scratch.get(gk, count));
+      HIP_TRY(scratch.get(ka, count)); HIP_TRY(scratch.get(kb, count));
+      HIP_TRY(scratch.get(sx, count)); HIP_TRY(scratch.get(spe, count)); HIP_TRY(scratch.get(sgk, count));
+      HIP_TRY(scratch.get(pa, count)); HIP_TRY(scratch.get(pb, count)); HIP_TRY(scratch.get(prd, count)); HIP_TRY(scratch.get(mrk, count));
+      size_t need = 0;
+      HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, xs, ka, pa, pb, size_t(count), 0, 64, st)); most = std::max(most, need);
+      return GCSA2_OK;
+    });
+    if(rc != GCSA2_OK) { return rc; }
     const dim3 lanes(grid_for(count));
-    HIP_TRY(hipMemsetAsync(lsize + n_groups, 0, sizeof(u64), st));
     HIP_TRY(hipMemsetAsync(mrk, 0xFF, count * sizeof(u32), st));                                                           // CHN_NO: no anchor is used
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, lsize, loff, size_t(n_groups + 1), st));
-    hipLaunchKernelGGL(k_chains_large_gather, lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, xs, pes, gk, pa);
-    LAUNCH_CHECK("k_chains_large_gather");
+    hipLaunchKernelGGL((k_anchors_large_gather<chn_place>), lanes, dim3(TPB), 0, st, loff, n_groups, count, goff, recs, hoff, hits, map, xs, pes, gk, pa);
+    LAUNCH_CHECK("k_anchors_large_gather");
     // by (group, unplaced, x, q, l): q << 32 | qe first, then stable sorts by x and by the group word
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, pes, ka, pa, pb, size_t(count), 0, 64, st));                     // pb: by (q, l)
     hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, xs, pb, count, ka);
@@ -6692,112 +6514,54 @@ int chains_core(const gcsa2_index* ix, const u64* goff, u64 n_groups, const gcsa
     LAUNCH_CHECK("k_clusters_large_take");
     // f and pred, then the order of the visit: by (group, f descending, place), two stable sorts again
     const dim3 grid(unsigned(std::min<u64>(n_groups, u64(ix->compute_units) * 8)));
-    hipLaunchKernelGGL(k_chains_large_dp, grid, dim3(64), 0, st, loff, lsize, n_groups, sx, spe, sgk, P, ka, prd, pa);
+    hipLaunchKernelGGL(k_chains_large_dp, grid, dim3(64), 0, st, loff, plan.lsize, n_groups, sx, spe, sgk, P, ka, prd, pa);
     LAUNCH_CHECK("k_chains_large_dp");
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, kb, pa, pb, size_t(count), 0, 51, st));                      // pb: by f descending
     hipLaunchKernelGGL(k_clusters_large_take, lanes, dim3(TPB), 0, st, sgk, pb, count, ka);
     LAUNCH_CHECK("k_clusters_large_take");
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, ka, kb, pb, pa, size_t(count), 0, 34, st));                      // pa: the order of the visit
-    hipLaunchKernelGGL(k_chains_large_finish, grid, dim3(TPB), 0, st, loff, lsize, n_groups, sx, spe, sgk, prd, mrk, pa, P, job.top, members, job.summaries,
-                       stat);
+    hipLaunchKernelGGL(k_chains_large_finish, grid, dim3(TPB), 0, st, loff, plan.lsize, n_groups, sx, spe, sgk, prd, mrk, pa, P, job.top, members, job.summaries,
+                       plan.stat);
     LAUNCH_CHECK("k_chains_large_finish");
   }
-  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  scratch.settled = true;
-  out->invalid_groups = host_stat[CLU_INVALID]; out->seeds = host_stat[CLU_SEEDS]; out->anchors = host_stat[CLU_ANCHORS];
-  out->unplaced = host_stat[CLU_UNPLACED]; out->chains = host_stat[CLU_CLUSTERS]; out->spilled = host_stat[CLU_SPILLED];
-  return GCSA2_OK;
+  return anchors_tail(plan, out, &gcsa2_chain_stats::chains, scratch, st);
 }
 
-// The fused chain forms: fused_hits, then the chain core with the seed offsets as the groups.
-int fused_chains_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
-                      u64 w, u64 hash_seed, u64 hit_max, int over, const ChainsJob& job, gcsa2_chain_stats* out, hipStream_t st)
+// the job's refusals of a fused or host form of n_groups reads
+int chains_job_checks(const gcsa2_index* ix, u64 shift, const void* coord_of_bin, u64 n_bins, const gcsa2_chain_params* params, const char* map_name, u64 n_groups)
 {
-  Scratch scratch(ix, st);
-  FusedHits f;
-  const int rc = fused_hits(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over,
-                            (minimizers ? "minimizer_chains" : "kmer_chains"), "chains", f, st);
-  if(rc != GCSA2_OK) { return rc; }
-  return chains_core(ix, f.seed_off, n_patterns, f.seeds, f.m, f.hit_off, f.hit_values, f.h, job, out, scratch, st);
+  const int rc = chains_checks(ix, shift, coord_of_bin, n_bins, params, map_name);
+  return (rc != GCSA2_OK ? rc : chains_member_check(params, n_groups));
 }
 
-int fused_chains_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
-                       u64 hash_seed, u64 hit_max, int over, const ChainsJob& job, const char* name, gcsa2_chain_stats* stats, void* stream)
+// the fused chain forms
+int fused_chains_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, const AnchorWindows& win, const ChainsJob& job,
+                       const char* name, gcsa2_chain_stats* stats, void* stream)
 {
-  u64 unused_seeds = 0, unused_hits = 0;
-  int rc = chains_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.params, "d_coord_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  rc = chains_member_check(job.params, n_patterns);
-  if(rc != GCSA2_OK) { return rc; }
-  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": d_offsets is NULL"); }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_chain_stats pre{};
-  pre.groups = n_patterns;
-  return stats_entry(name, ix, stats, pre, n_patterns == 0, [&](gcsa2_chain_stats& sums) -> int
+  return fused_anchors_entry(ix, d_patterns, d_offsets, n_patterns, win, job, name, "chains",
+                             [&] { return chains_job_checks(ix, job.shift, job.coord_of_bin, job.n_bins, job.params, "d_coord_of_bin", n_patterns); }, chains_core,
+                             stats, stream);
+}
+
+// both host forms: the top rows, the member rows (only if member_cap > 0) and the summaries of every piece
+int chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, const AnchorWindows& win, u64 shift,
+                 const uint64_t* coord_of_bin, u64 n_bins, const gcsa2_chain_params* params, gcsa2_chain* top, gcsa2_chain_anchor* members,
+                 gcsa2_chain_summary* summaries, gcsa2_chain_stats* stats, const char* name)
+{
+  const u64 top_n = (params != nullptr ? params->top_n : 0), member_cap = (params != nullptr ? params->member_cap : 0);
+  const PieceOutput outs[] = {{top, top_n, sizeof(gcsa2_chain)}, {members, top_n * member_cap, sizeof(gcsa2_chain_anchor)}, {summaries, 1, sizeof(gcsa2_chain_summary)}};
+  return anchors_batch(ix, patterns, offsets, n_patterns, win, coord_of_bin, n_bins, outs, stats, name,
+                       [&] { return chains_job_checks(ix, shift, coord_of_bin, n_bins, params, "coord_of_bin", n_patterns); },
+                       [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, const u64* d_map, void* const* d, gcsa2_chain_stats* done) -> int
   {
-    return fused_chains_core(ix, d_patterns, d_offsets, n_patterns, k, stride, minimizers, w, hash_seed, hit_max, over, job, &sums, static_cast<hipStream_t>(stream));
+    gcsa2_chain* d_top = static_cast<gcsa2_chain*>(d[0]);
+    gcsa2_chain_anchor* d_mem = static_cast<gcsa2_chain_anchor*>(d[1]);
+    gcsa2_chain_summary* d_sum = static_cast<gcsa2_chain_summary*>(d[2]);
+    return (win.minimizers ? gcsa2_minimizer_chains_device(ix, d_pat, d_off, p.count, win.k, win.w, win.hash_seed, win.hit_max, win.over, shift, d_map, n_bins, params,
+                                                           d_top, d_mem, d_sum, done, p.stream)
+                           : gcsa2_kmer_chains_device(ix, d_pat, d_off, p.count, win.k, win.stride, win.hit_max, win.over, shift, d_map, n_bins, params, d_top, d_mem,
+                                                      d_sum, done, p.stream));
   });
-}
-
-// Both host forms, as clusters_batch: the coordinate map goes to the device once; each piece is one fused device call on its
-// thread's stream into device rows, member rows and summaries of its own, copied to the piece's place in the caller's arrays.
-int chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers, u64 w,
-                 u64 hash_seed, u64 hit_max, int over, u64 shift, const uint64_t* coord_of_bin, u64 n_bins, const gcsa2_chain_params* params, gcsa2_chain* top,
-                 gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries, gcsa2_chain_stats* stats, const char* name)
-{
-  u64 unused_seeds = 0, unused_hits = 0;
-  int rc = chains_checks(ix, shift, coord_of_bin, n_bins, params, "coord_of_bin");
-  if(rc != GCSA2_OK) { return rc; }
-  rc = chains_member_check(params, n_patterns);
-  if(rc != GCSA2_OK) { return rc; }
-  rc = (minimizers ? minimizer_hits_checks(ix, k, w, over, &unused_seeds, &unused_hits) : kmer_hits_checks(ix, k, stride, over, &unused_seeds, &unused_hits));
-  if(rc != GCSA2_OK) { return rc; }
-  if(n_patterns >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more reads in one call; split the batch"); }
-  gcsa2_chain_stats sums{};
-  if(n_patterns == 0) { if(stats != nullptr) { *stats = sums; } return GCSA2_OK; }
-  if(offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, std::string(name) + ": offsets is NULL"); }
-  rc = reads_ok(patterns, offsets, n_patterns, name);
-  if(rc != GCSA2_OK) { return rc; }
-  try {   // no C++ exception may cross the C boundary
-  g_error.clear();
-  if(host_windows(offsets, n_patterns, k, (minimizers ? 1 : stride)) >= (u64(1) << 32))
-  {
-    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more windows in one call; split the batch");
-  }
-  DeviceGuard guard(ix->device);
-  DBuf<u64> d_map;
-  HIP_TRY(d_map.alloc(n_bins));
-  HIP_TRY(hipMemcpy(d_map.p, coord_of_bin, n_bins * sizeof(u64), hipMemcpyHostToDevice));
-  const u64 top_n = params->top_n, per_read = (members != nullptr ? top_n * params->member_cap : 0);      // member entries of a read
-  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
-  std::vector<gcsa2_chain_stats> done(cut.size() - 1);
-  rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
-  {
-    DBuf<u8> d_pat; DBuf<u64> d_off; DBuf<gcsa2_chain> d_top; DBuf<gcsa2_chain_anchor> d_mem; DBuf<gcsa2_chain_summary> d_sum;
-    if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
-    hipError_t e = (top != nullptr ? d_top.alloc(p.count * top_n) : hipSuccess);
-    if(e == hipSuccess && per_read > 0) { e = d_mem.alloc(p.count * per_read); }
-    if(e == hipSuccess && summaries != nullptr) { e = d_sum.alloc(p.count); }
-    if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
-    const int piece_rc = (minimizers ? gcsa2_minimizer_chains_device(ix, d_pat.p, d_off.p, p.count, k, w, hash_seed, hit_max, over, shift, d_map.p, n_bins, params,
-                                                                      d_top.p, d_mem.p, d_sum.p, &done[p.c], p.stream)
-                                     : gcsa2_kmer_chains_device(ix, d_pat.p, d_off.p, p.count, k, stride, hit_max, over, shift, d_map.p, n_bins, params,
-                                                                 d_top.p, d_mem.p, d_sum.p, &done[p.c], p.stream));
-    if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
-    if(top != nullptr) { e = hipMemcpy(top + p.b * top_n, d_top.p, p.count * top_n * sizeof(gcsa2_chain), hipMemcpyDeviceToHost); }
-    if(e == hipSuccess && per_read > 0) { e = hipMemcpy(members + p.b * per_read, d_mem.p, p.count * per_read * sizeof(gcsa2_chain_anchor), hipMemcpyDeviceToHost); }
-    if(e == hipSuccess && summaries != nullptr) { e = hipMemcpy(summaries + p.b, d_sum.p, p.count * sizeof(gcsa2_chain_summary), hipMemcpyDeviceToHost); }
-    if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
-    return true;
-  });
-  if(rc != GCSA2_OK) { return rc; }
-  for(const gcsa2_chain_stats& s : done) { sum_stats(sums, s); }
-  if(stats != nullptr) { *stats = sums; }
-  return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(name) + ": " + e.what()); }
 }
 
 }  // namespace
@@ -6811,13 +6575,8 @@ int gcsa2_seed_chains_device(const gcsa2_index* ix, const uint64_t* d_group_offs
 {
   int rc = chains_checks(ix, shift, d_coord_of_bin, n_bins, params, "d_coord_of_bin");
   if(rc != GCSA2_OK) { return rc; }
-  if(n_groups > 0 && d_group_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_group_offsets is NULL"); }
-  if(n_seeds > 0 && d_seeds == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_seeds is NULL"); }
-  if(n_seeds > 0 && d_hit_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_hit_offsets is NULL"); }
-  if(n_hits > 0 && d_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: d_hits is NULL"); }
-  if(n_groups >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more groups in one call; split the batch"); }
-  if(n_seeds >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more seeds in one call; split the batch"); }
-  if(n_hits >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "seed_chains: 2^32 or more hits in one call; split the batch"); }
+  rc = seed_form_checks("seed_chains", d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits);
+  if(rc != GCSA2_OK) { return rc; }
   rc = chains_member_check(params, n_groups);
   if(rc != GCSA2_OK) { return rc; }
   gcsa2_chain_stats pre{};
@@ -6836,7 +6595,7 @@ int gcsa2_kmer_chains_device(const gcsa2_index* ix, const uint8_t* d_patterns, c
                              gcsa2_chain* d_top, gcsa2_chain_anchor* d_members, gcsa2_chain_summary* d_summaries, gcsa2_chain_stats* stats, void* stream)
 {
   const ChainsJob job{shift, d_coord_of_bin, n_bins, params, d_top, d_members, d_summaries};
-  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, job, "kmer_chains", stats, stream);
+  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, AnchorWindows{k, stride, false, 0, 0, hit_max, over}, job, "kmer_chains", stats, stream);
 }
 
 int gcsa2_minimizer_chains_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
@@ -6845,15 +6604,15 @@ int gcsa2_minimizer_chains_device(const gcsa2_index* ix, const uint8_t* d_patter
                                   gcsa2_chain_stats* stats, void* stream)
 {
   const ChainsJob job{shift, d_coord_of_bin, n_bins, params, d_top, d_members, d_summaries};
-  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, job, "minimizer_chains", stats, stream);
+  return fused_chains_entry(ix, d_patterns, d_offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, job, "minimizer_chains", stats, stream);
 }
 
 int gcsa2_kmer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t stride,
                             uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins, const gcsa2_chain_params* params,
                             gcsa2_chain* top, gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries, gcsa2_chain_stats* stats)
 {
-  return chains_batch(ix, patterns, offsets, n_patterns, k, stride, false, 0, 0, hit_max, over, shift, coord_of_bin, n_bins, params, top, members, summaries, stats,
-                      "gcsa2_kmer_chains_batch");
+  return chains_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, stride, false, 0, 0, hit_max, over}, shift, coord_of_bin, n_bins, params, top, members,
+                      summaries, stats, "gcsa2_kmer_chains_batch");
 }
 
 int gcsa2_minimizer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
@@ -6861,8 +6620,8 @@ int gcsa2_minimizer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns,
                                  const gcsa2_chain_params* params, gcsa2_chain* top, gcsa2_chain_anchor* members, gcsa2_chain_summary* summaries,
                                  gcsa2_chain_stats* stats)
 {
-  return chains_batch(ix, patterns, offsets, n_patterns, k, 1, true, w, hash_seed, hit_max, over, shift, coord_of_bin, n_bins, params, top, members, summaries, stats,
-                      "gcsa2_minimizer_chains_batch");
+  return chains_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, shift, coord_of_bin, n_bins, params, top, members,
+                      summaries, stats, "gcsa2_minimizer_chains_batch");
 }
 
 }  // extern "C"

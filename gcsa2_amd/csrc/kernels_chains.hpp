@@ -1,11 +1,12 @@
 // kernels_chains.hpp -- seed chains (gcsa2_seed_chains_device and its fused forms, include/gcsa2_hip_chains.h): per group of
 // seed records the top_n colinear chains of its anchors, by a dynamic program over the anchors in (x, q, l) order.  Included by
 // gcsa2_hip.hip after kernels_clusters.hpp, whose plan kernel (k_clusters_plan: the groups are validated there, once), placement
-// (clu_place), bitonic sort, top row (clu_top_insert, CluShared) and counters (CLU_*; CLU_CLUSTERS counts the chains) it uses.
+// (clu_place), large gather (k_anchors_large_gather, clu_large_placed), zero rows (clu_zero), bitonic sort, top row
+// (clu_top_insert, CluShared) and counters (CLU_*, clu_flush; CLU_CLUSTERS counts the chains) it uses.
 //
 // Data flow: k_clusters_plan -> k_chains_lds (one workgroup per group of up to `cap` anchors: gather and place, bitonic sort by
 // (x, q << 32 | qe), chn_dp, bitonic sort of the places by (f descending, place), chn_finish) -> for the groups above the
-// capacity k_chains_large_gather, three stable radix sorts into (group, x, q, l) order, k_chains_large_dp (one wavefront per
+// capacity k_anchors_large_gather<chn_place>, three stable radix sorts into (group, x, q, l) order, k_chains_large_dp (one wavefront per
 // group: chn_dp over global memory), two stable radix sorts into (group, f descending, place) order, k_chains_large_finish (one
 // workgroup per group: chn_finish over global memory).  chn_dp and chn_finish are the same code over a view of LDS or of global
 // memory.
@@ -127,25 +128,17 @@ __device__ void chn_dp(const View& view, u64 n, const ChnParams& P)
   }
 }
 
-// the zero row, member rows and summary {0, unplaced, 0} of an invalid group or one without a placed anchor
+// clu_zero -- the zero row and the summary {0, unplaced, 0} of an invalid group or one without a placed anchor -- and the
+// zero member rows
 template<u32 T>
 __device__ __forceinline__ void chn_zero(u64 g, const ChnParams& P, gcsa2_chain* __restrict__ top, gcsa2_chain_anchor* __restrict__ members,
                                          gcsa2_chain_summary* __restrict__ summaries, u64 unplaced)
 {
-  if(top != nullptr)
-  {
-    u64* row = reinterpret_cast<u64*>(top + g * P.top_n);
-    for(u32 word = threadIdx.x; word < P.top_n * 8; word += T) { row[word] = 0; }
-  }
+  clu_zero<T>(g, P.top_n, top, summaries, unplaced);
   if(members != nullptr)
   {
     u64* rows = reinterpret_cast<u64*>(members + g * P.top_n * P.member_cap);
     for(u64 word = threadIdx.x; word < 2 * P.top_n * P.member_cap; word += T) { rows[word] = 0; }
-  }
-  if(summaries != nullptr && threadIdx.x == 0)
-  {
-    u64* dst = reinterpret_cast<u64*>(summaries + g);
-    dst[0] = 0; dst[1] = unplaced; dst[2] = 0;
   }
 }
 
@@ -270,7 +263,7 @@ __device__ u64 chn_finish(const View& view, u64 n, u64 anchors_all, u64 g, const
 //   3. chn_dp by wavefront 0: pm = f << 13 | pred
 //   4. sk = (F_LIMIT - 1 - f) << 12 | place and pm = pred | no mark; bitonic sort of sk
 //   5. chn_finish
-// Three atomics per workgroup for the stats.
+// Three atomics per workgroup for the stats (clu_flush).
 template<u32 T>
 __global__ __launch_bounds__(T) void k_chains_lds(const u64* __restrict__ goff, u64 n_groups, const u64* __restrict__ seeds, const u64* __restrict__ hoff,
                                                     const u64* __restrict__ hits, const u64* __restrict__ info, CluMap map, ChnParams P, u32 cap,
@@ -346,44 +339,12 @@ __global__ __launch_bounds__(T) void k_chains_lds(const u64* __restrict__ goff, 
     const u64 chains = chn_finish<T>(view, n, total, g, P, top, members, summaries, sh);
     if(threadIdx.x == 0) { all_chains += chains; }
   }
-  if(threadIdx.x == 0)
-  {
-    if(all_anchors != 0) { atomicAdd(stat + CLU_ANCHORS, (unsigned long long)all_anchors); }
-    if(all_unplaced != 0) { atomicAdd(stat + CLU_UNPLACED, (unsigned long long)all_unplaced); }
-    if(all_chains != 0) { atomicAdd(stat + CLU_CLUSTERS, (unsigned long long)all_chains); }
-  }
+  clu_flush(stat, all_anchors, all_unplaced, all_chains);
 }
 
 // ---- the large path: the groups above the capacity, all at once ---------------------------------------------------------------
-// loff, lsize and the places [loff[g], loff[g + 1]) of a group: as in kernels_clusters.hpp.
-
-// One lane per anchor, as k_clusters_large_gather: xs = x, pes = q << 32 | qe (CLU_NONE both for an unplaced anchor) and
-// gk = group << 1 | unplaced.
-__global__ __launch_bounds__(TPB) void k_chains_large_gather(const u64* __restrict__ loff, u64 n_groups, u64 count, const u64* __restrict__ goff,
-                                                             const u64* __restrict__ seeds, const u64* __restrict__ hoff, const u64* __restrict__ hits,
-                                                             CluMap map, u64* __restrict__ xs, u64* __restrict__ pes, u64* __restrict__ gk,
-                                                             u32* __restrict__ place)
-{
-  const u64 e = u64(blockIdx.x) * TPB + threadIdx.x;
-  if(e >= count) { return; }
-  const u64 g = clu_seed_of(loff, 0, n_groups, e), first = goff[g], last = goff[g + 1], h = hoff[first] + (e - loff[g]), i = clu_seed_of(hoff, first, last, h);
-  u64 x = CLU_NONE, p = CLU_NONE;
-  const bool placed = chn_place(map, hits[h], seeds[5 * i], seeds[5 * i + 1], x, p);
-  xs[e] = (placed ? x : CLU_NONE); pes[e] = (placed ? p : CLU_NONE); gk[e] = (g << 1) | (placed ? 0 : 1);
-  place[e] = u32(e);
-}
-
-// the number of placed anchors of a large group: the first of its `total` places with the unplaced bit
-__device__ __forceinline__ u64 chn_large_placed(const u64* __restrict__ gk, u64 begin, u64 total)
-{
-  u64 lo = 0, hi = total;
-  while(lo < hi)
-  {
-    const u64 mid = lo + (hi - lo) / 2;
-    if((gk[begin + mid] & 1) == 0) { lo = mid + 1; } else { hi = mid; }
-  }
-  return lo;
-}
+// loff, lsize and the places [loff[g], loff[g + 1]) of a group: as in kernels_clusters.hpp, whose k_anchors_large_gather<chn_place>
+// fills xs = x, pes = q << 32 | qe (CLU_NONE both for an unplaced anchor) and gk = group << 1 | unplaced.
 
 // One wavefront per group above the capacity, behind the sorts by (group, unplaced, x, q, l): chn_dp over global memory.  It
 // also sets what the next sorts take: fkey (CHN_F_LIMIT for an unplaced anchor: behind every placed one) and place = the index.
@@ -395,7 +356,7 @@ __global__ __launch_bounds__(64) void k_chains_large_dp(const u64* __restrict__ 
   {
     const u64 total = lsize[g];
     if(total == 0) { continue; }
-    const u64 begin = loff[g], n = chn_large_placed(gk, begin, total);
+    const u64 begin = loff[g], n = clu_large_placed(gk, begin, total);
     const ChnGlobalView view{xs + begin, pes + begin, fkey + begin, prd + begin, nullptr, nullptr, begin};
     chn_dp(view, n, P);
     for(u64 i = n + threadIdx.x; i < total; i += 64) { fkey[begin + i] = CHN_F_LIMIT; }
@@ -418,7 +379,7 @@ __global__ __launch_bounds__(TPB) void k_chains_large_finish(const u64* __restri
   {
     const u64 total = lsize[g];
     if(total == 0) { continue; }
-    const u64 begin = loff[g], n = chn_large_placed(gk, begin, total);
+    const u64 begin = loff[g], n = clu_large_placed(gk, begin, total);
     if(n == 0)
     {
       chn_zero<TPB>(g, P, top, members, summaries, total);
@@ -429,12 +390,7 @@ __global__ __launch_bounds__(TPB) void k_chains_large_finish(const u64* __restri
     const u64 chains = chn_finish<TPB>(view, n, total, g, P, top, members, summaries, sh);
     if(threadIdx.x == 0) { all_anchors += n; all_unplaced += total - n; all_chains += chains; }
   }
-  if(threadIdx.x == 0)
-  {
-    if(all_anchors != 0) { atomicAdd(stat + CLU_ANCHORS, (unsigned long long)all_anchors); }
-    if(all_unplaced != 0) { atomicAdd(stat + CLU_UNPLACED, (unsigned long long)all_unplaced); }
-    if(all_chains != 0) { atomicAdd(stat + CLU_CLUSTERS, (unsigned long long)all_chains); }
-  }
+  clu_flush(stat, all_anchors, all_unplaced, all_chains);
 }
 
 }  // namespace

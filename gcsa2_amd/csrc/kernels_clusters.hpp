@@ -5,10 +5,14 @@
 // Data flow: k_clusters_plan (one wavefront per group: the group is checked against n_seeds and n_hits ONCE, here; info[g] is
 // its anchor count or "invalid", lsize[g] the same count if the group is above the LDS capacity) -> k_clusters_lds (one
 // workgroup per group: gather, bitonic sort by diagonal, heads, bitonic sort by (cluster, position), segment sums, top row) ->
-// for the groups above the capacity the same steps device-wide: k_clusters_large_gather, two radix sorts by (group, diagonal),
+// for the groups above the capacity the same steps device-wide: k_anchors_large_gather, two radix sorts by (group, diagonal),
 // k_clusters_large_take / _heads, a max-scan for the cluster of every anchor, a radix sort by (cluster, position),
 // k_clusters_large_ends and a max-scan for the running end, k_clusters_large_cover and a sum-scan for covered and starts,
 // then k_clusters_large_score (one workgroup per group).  Both paths end in clu_score, over a view of LDS or of global memory.
+//
+// Shared with the seed chains (kernels_chains.hpp): the plan, k_anchors_large_gather<clu_place or chn_place>, clu_large_placed,
+// clu_zero, clu_flush.  Not the group loop and LDS gather of the two LDS kernels: folded, the chain kernels ran slower
+// (profiles/anchor_groups_refactor.md).
 //
 // A cluster is named by the sorted place of its first anchor (its HEAD): heads ascend with the diagonal and, in the large
 // path, with the group, so "sort by (group, cluster, position)" is one 64-bit key head << 32 | position, and the running
@@ -48,6 +52,8 @@ __device__ __forceinline__ bool clu_place(const CluMap& map, u64 v, u64 pos, u64
   pe = (pos << 32) | (pos + len);
   return true;
 }
+// a placer, clu_place or the chains' chn_place: the gathers below are written once and take it as a template argument
+using CluPlaceFn = bool(const CluMap&, u64, u64, u64, u64&, u64&);
 
 // the seed of hit h: the last i in [first, last) with hoff[i] <= h (hoff[first] <= h < hoff[last], the offsets do not decrease)
 __device__ __forceinline__ u64 clu_seed_of(const u64* __restrict__ hoff, u64 first, u64 last, u64 h)
@@ -242,10 +248,11 @@ __device__ u64 clu_score(const View& view, u64 begin, u64 end, u64 anchors_all, 
   return clusters;
 }
 
-// the zero row of an invalid group or one without a placed anchor, and its summary {0, unplaced, 0}
-template<u32 T>
-__device__ __forceinline__ void clu_zero(u64 g, u32 top_n, gcsa2_cluster* __restrict__ top, gcsa2_cluster_summary* __restrict__ summaries, u64 unplaced)
+// the zero row (of clusters, or of chains) of an invalid group or one without a placed anchor, and its summary {0, unplaced, 0}
+template<u32 T, class Row, class Summary>
+__device__ __forceinline__ void clu_zero(u64 g, u32 top_n, Row* __restrict__ top, Summary* __restrict__ summaries, u64 unplaced)
 {
+  static_assert(sizeof(Row) == 64 && sizeof(Summary) == 24, "eight words a row entry, three a summary");
   if(top != nullptr)
   {
     u64* row = reinterpret_cast<u64*>(top + g * top_n);
@@ -255,6 +262,17 @@ __device__ __forceinline__ void clu_zero(u64 g, u32 top_n, gcsa2_cluster* __rest
   {
     u64* dst = reinterpret_cast<u64*>(summaries + g);
     dst[0] = 0; dst[1] = unplaced; dst[2] = 0;
+  }
+}
+
+// what a workgroup counted over its groups: three atomics at most, by thread 0 (the other threads' sums are not looked at)
+__device__ __forceinline__ void clu_flush(unsigned long long* __restrict__ stat, u64 anchors, u64 unplaced, u64 clusters)
+{
+  if(threadIdx.x == 0)
+  {
+    if(anchors != 0) { atomicAdd(stat + CLU_ANCHORS, (unsigned long long)anchors); }
+    if(unplaced != 0) { atomicAdd(stat + CLU_UNPLACED, (unsigned long long)unplaced); }
+    if(clusters != 0) { atomicAdd(stat + CLU_CLUSTERS, (unsigned long long)clusters); }
   }
 }
 
@@ -319,7 +337,7 @@ __device__ __forceinline__ void clu_bitonic(u64* a, u64* b, u32 n)
 //      covered grows by what the anchor adds beyond that maximum, starts by a change of (head, position); per cluster and
 //      thread one LDS add into acc[head] = covered << 26 | anchors << 13 | starts
 //   6. clu_score
-// Three atomics per workgroup for the stats.
+// Three atomics per workgroup for the stats (clu_flush).
 template<u32 T>
 __global__ __launch_bounds__(T) void k_clusters_lds(const u64* __restrict__ goff, u64 n_groups, const u64* __restrict__ seeds, const u64* __restrict__ hoff,
                                                       const u64* __restrict__ hits, const u64* __restrict__ info, CluMap map, u64 band, u32 top_n, u32 cap,
@@ -421,33 +439,42 @@ __global__ __launch_bounds__(T) void k_clusters_lds(const u64* __restrict__ goff
     const u64 clusters = clu_score<T>(view, 0, n, total, g, top_n, top, summaries, sh);
     if(threadIdx.x == 0) { all_clusters += clusters; }
   }
-  if(threadIdx.x == 0)
-  {
-    if(all_anchors != 0) { atomicAdd(stat + CLU_ANCHORS, (unsigned long long)all_anchors); }
-    if(all_unplaced != 0) { atomicAdd(stat + CLU_UNPLACED, (unsigned long long)all_unplaced); }
-    if(all_clusters != 0) { atomicAdd(stat + CLU_CLUSTERS, (unsigned long long)all_clusters); }
-  }
+  clu_flush(stat, all_anchors, all_unplaced, all_clusters);
 }
 
 // ---- the large path: the groups above the capacity, all at once ---------------------------------------------------------------
 // loff (n_groups + 1): the exclusive scan of lsize; the anchors of group g are the places [loff[g], loff[g + 1]) of every
 // array here, `count` (< 2^32) in all, and stay there through every sort: a sort key starts with the group.
 
-// One lane per anchor: its group by a search over loff, then as step 1 above.  gk = group << 1 | unplaced: the placed anchors
-// of a group sort in front of the others.
-__global__ __launch_bounds__(TPB) void k_clusters_large_gather(const u64* __restrict__ loff, u64 n_groups, u64 count, const u64* __restrict__ goff,
-                                                               const u64* __restrict__ seeds, const u64* __restrict__ hoff, const u64* __restrict__ hits,
-                                                               CluMap map, u64* __restrict__ dk, u64* __restrict__ pe, u64* __restrict__ gk,
-                                                               u32* __restrict__ place)
+// One lane per anchor, for the clusters (clu_place) and for the chains (chn_place): its group by a search over loff, then as
+// step 1 of the LDS kernels.  (wa, wb): the two words of PLACE, CLU_NONE both for an unplaced anchor; gk = group << 1 | unplaced: the
+// placed anchors of a group sort in front of the others.
+template<CluPlaceFn PLACE>
+__global__ __launch_bounds__(TPB) void k_anchors_large_gather(const u64* __restrict__ loff, u64 n_groups, u64 count, const u64* __restrict__ goff,
+                                                              const u64* __restrict__ seeds, const u64* __restrict__ hoff, const u64* __restrict__ hits,
+                                                              CluMap map, u64* __restrict__ wa, u64* __restrict__ wb, u64* __restrict__ gk,
+                                                              u32* __restrict__ place)
 {
   const u64 e = u64(blockIdx.x) * TPB + threadIdx.x;
   if(e >= count) { return; }
   // the last g with loff[g] <= e: loff[0] = 0, loff[n_groups] = count > e (the search of clu_seed_of over the group sizes)
   const u64 g = clu_seed_of(loff, 0, n_groups, e), first = goff[g], last = goff[g + 1], h = hoff[first] + (e - loff[g]), i = clu_seed_of(hoff, first, last, h);
   u64 key = CLU_NONE, p = CLU_NONE;
-  const bool placed = clu_place(map, hits[h], seeds[5 * i], seeds[5 * i + 1], key, p);
-  dk[e] = (placed ? key : CLU_NONE); pe[e] = (placed ? p : CLU_NONE); gk[e] = (g << 1) | (placed ? 0 : 1);
+  const bool placed = PLACE(map, hits[h], seeds[5 * i], seeds[5 * i + 1], key, p);
+  wa[e] = (placed ? key : CLU_NONE); wb[e] = (placed ? p : CLU_NONE); gk[e] = (g << 1) | (placed ? 0 : 1);
   place[e] = u32(e);
+}
+
+// the number of placed anchors of a large group behind the sorts: the first of its `total` places with the unplaced bit
+__device__ __forceinline__ u64 clu_large_placed(const u64* __restrict__ gk, u64 begin, u64 total)
+{
+  u64 lo = 0, hi = total;
+  while(lo < hi)
+  {
+    const u64 mid = lo + (hi - lo) / 2;
+    if((gk[begin + mid] & 1) == 0) { lo = mid + 1; } else { hi = mid; }
+  }
+  return lo;
 }
 
 __global__ __launch_bounds__(TPB) void k_clusters_large_take(const u64* __restrict__ src, const u32* __restrict__ place, u64 count, u64* __restrict__ dst)
@@ -514,14 +541,7 @@ __global__ __launch_bounds__(TPB) void k_clusters_large_score(const u64* __restr
   {
     const u64 total = lsize[g];
     if(total == 0) { continue; }
-    const u64 begin = loff[g];
-    u64 lo = 0, hi = total;                                  // the number of placed anchors: the first place with the unplaced bit
-    while(lo < hi)
-    {
-      const u64 mid = lo + (hi - lo) / 2;
-      if((gk[begin + mid] & 1) == 0) { lo = mid + 1; } else { hi = mid; }
-    }
-    const u64 n = lo;
+    const u64 begin = loff[g], n = clu_large_placed(gk, begin, total);
     if(n == 0)
     {
       clu_zero<TPB>(g, top_n, top, summaries, total);
@@ -532,12 +552,7 @@ __global__ __launch_bounds__(TPB) void k_clusters_large_score(const u64* __restr
     const u64 clusters = clu_score<TPB>(view, begin, begin + n, total, g, top_n, top, summaries, sh);
     if(threadIdx.x == 0) { all_anchors += n; all_unplaced += total - n; all_clusters += clusters; }
   }
-  if(threadIdx.x == 0)
-  {
-    if(all_anchors != 0) { atomicAdd(stat + CLU_ANCHORS, (unsigned long long)all_anchors); }
-    if(all_unplaced != 0) { atomicAdd(stat + CLU_UNPLACED, (unsigned long long)all_unplaced); }
-    if(all_clusters != 0) { atomicAdd(stat + CLU_CLUSTERS, (unsigned long long)all_clusters); }
-  }
+  clu_flush(stat, all_anchors, all_unplaced, all_clusters);
 }
 
 }  // namespace
