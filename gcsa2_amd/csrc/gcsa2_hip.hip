@@ -206,6 +206,12 @@ constexpr bool JUMP_DEFAULT_FIND_ONLY = true;
 // of what is free): `bytes` more must leave a sixteenth of the device's memory free for the caller's batches and the
 // handle's scratch pool -- 18 GB of a 288 GB device, where the 91.6 GB table of a 5.73 G-node index goes on top of a 175 GB image.
 inline bool jump_table_fits(u64 bytes, u64 free_bytes, u64 total_bytes) { return bytes <= free_bytes && free_bytes - bytes >= total_bytes / 16; }
+// Steps behind the middle node slot of a jump entry (DevImage::jump_mid).  6 saves a lookup on chain tails of 6 and 7
+// characters and leaves tails of 2 and 3 to the pair step; that pays where a lookup is an HBM request, i.e. where the
+// table does not stay in the last-level cache (the 256 MiB Infinity Cache), and where a pair step exists to take two
+// characters in one request.  Everywhere else the entry keeps the node after 2 steps.
+constexpr u64 LAST_LEVEL_CACHE_BYTES = u64(256) << 20;
+inline u32 jump_mid_default(u64 nodes, bool pair_blocks) { return pair_blocks && nodes * sizeof(ulonglong2) > LAST_LEVEL_CACHE_BYTES ? 6 : 2; }
 
 inline void launch_walk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, const u64* node_off, const u64* raw_off,
                         u64 total_nodes, u64* values, u64* owners, hipStream_t stream);
@@ -1126,11 +1132,13 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
   // a sixteenth of the device free (jump_table_fits); GCSA2_JUMP_TABLE=0 switches it off.  Two builders with identical output: doubling
   // (1 -> 2 -> 4 -> 8 steps) through a second buffer that is released afterwards where both buffers pass the
   // free-memory test, otherwise one pass of chain walks into the table itself (k_jump_walk); GCSA2_JUMP_BUILD=double|walk
-  // forces one of them (tests).  A table that cannot be had is left out without an error.
-  ix->img.jump_tab = nullptr;
+  // forces one of them (tests).  A table that cannot be had is left out without an error.  The middle slot of its entries
+  // holds the node after jump_mid steps: jump_mid_default(), or GCSA2_JUMP_MID=2|6 (any other value is ignored).
+  ix->img.jump_tab = nullptr; ix->img.jump_mid = 2;
   {
     const char* env = std::getenv("GCSA2_JUMP_TABLE");
     const char* how = std::getenv("GCSA2_JUMP_BUILD");
+    const char* mid = std::getenv("GCSA2_JUMP_MID");
     size_t free_bytes = 0, total_bytes = 0;
     const u64 n = ix->img.n, bytes = n * sizeof(ulonglong2);
     const bool wanted = (env != nullptr && *env != 0 ? std::atoi(env) != 0 : JUMP_DEFAULT_FIND_ONLY && !ix->img.has_samples);
@@ -1141,6 +1149,8 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       bool doubling = jump_table_fits(2 * bytes, free_bytes, total_bytes);
       if(how != nullptr && std::strcmp(how, "walk") == 0) { doubling = false; }
       if(how != nullptr && std::strcmp(how, "double") == 0) { doubling = true; }        // a failed allocation still ends without a table
+      ix->img.jump_mid = jump_mid_default(n, ix->img.flp != nullptr);
+      if(mid != nullptr && (std::strcmp(mid, "2") == 0 || std::strcmp(mid, "6") == 0)) { ix->img.jump_mid = u32(mid[0] - '0'); }
       void* other = nullptr;
       hipError_t e = hipMalloc(&ix->d_jump, bytes);
       if(e == hipSuccess && doubling) { e = hipMalloc(&other, bytes); }
@@ -1158,7 +1168,7 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
         for(u64 first = 0; first < n && e == hipSuccess; first += slice)
         {
           u64 count = (n - first < slice ? n - first : slice);
-          hipLaunchKernelGGL(k_jump_double, dim3(grid_for(count)), dim3(TPB), 0, nullptr, a, n, first, have, b);
+          hipLaunchKernelGGL(k_jump_double, dim3(grid_for(count)), dim3(TPB), 0, nullptr, a, n, first, have, ix->img.jump_mid, b);
           e = hipGetLastError();
         }
         std::swap(a, b);
@@ -1174,7 +1184,7 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       else
       {
         if(ix->d_jump) { (void)hipFree(ix->d_jump); } if(other) { (void)hipFree(other); }
-        ix->d_jump = nullptr; (void)hipGetLastError();
+        ix->d_jump = nullptr; ix->img.jump_mid = 2; (void)hipGetLastError();
       }
     }
   }
@@ -1443,6 +1453,8 @@ uint64_t gcsa2_pair_block_bytes(const gcsa2_index* ix) { return ix->img.flp != n
 uint64_t gcsa2_find_block_bytes(const gcsa2_index*) { return FLB_BYTES; }
 uint64_t gcsa2_kmer_table_k(const gcsa2_index* ix) { return ix->img.kmer_k; }
 uint64_t gcsa2_jump_table_bytes(const gcsa2_index* ix) { return ix->img.jump_tab != nullptr ? ix->img.n * sizeof(ulonglong2) : 0; }
+int gcsa2_jump_mid(const gcsa2_index* ix) { return int(ix->img.jump_mid); }
+int gcsa2_jump_mid_default(uint64_t nodes, int pair_blocks) { return int(jump_mid_default(nodes, pair_blocks != 0)); }
 uint64_t gcsa2_locate_table_bytes(const gcsa2_index* ix) { return ix->img.locate_tab != nullptr ? ix->img.n * sizeof(u64) : 0; }
 
 int gcsa2_lf_device(const gcsa2_index* ix, const uint64_t* d_in, const uint8_t* d_comps, uint64_t nq,

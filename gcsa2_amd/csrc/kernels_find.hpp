@@ -341,20 +341,23 @@ __device__ __forceinline__ PairEnd eval_staged(const ulonglong2* wave_stage, u32
 
 // Jump table entry (16 bytes per path node): the forced chain of up to 8 LF steps out of a node -- every
 // node on it has a single incoming label, a fast character -- with the nodes reached after all `len`
-// steps, after 4 steps (len >= 4) and after 2 steps (len >= 2), so that a pattern with fewer characters
-// left than the chain is long can still take a prefix of it.  Nodes are 36-bit (n < 2^36).
+// steps, after 4 steps (len >= 4) and after `mid` steps (len >= mid), so that a pattern with fewer characters
+// left than the chain is long can still take a prefix of it.  mid is DevImage::jump_mid, one value per image: 2, or 6
+// where a saved lookup is a saved HBM request (gcsa2_index_create) -- a tail of 6 or 7 characters on a full chain is
+// then one lookup, not a take of 4 and a take of 2, and a tail of 2 or 3 is the pair step it costs anyway.  The middle
+// slot is zero when len < mid.  Nodes are 36-bit (n < 2^36).
 //   x: [0,36) node after len steps   [36,64) low 28 bits of the node after 4 steps
-//   y: [0,8) its high 8 bits   [8,44) node after 2 steps   [44,60) labels (comp - 1), 2 bits per step   [60,64) len
+//   y: [0,8) its high 8 bits   [8,44) node after mid steps   [44,60) labels (comp - 1), 2 bits per step   [60,64) len
 constexpr u32 JUMP_MAX = 8;
 constexpr u64 JUMP_NODE_BITS = 36, JUMP_NODE_MASK = (u64(1) << JUMP_NODE_BITS) - 1;
 __device__ __forceinline__ u64 jt_end(ulonglong2 e) { return e.x & JUMP_NODE_MASK; }
 __device__ __forceinline__ u64 jt_after4(ulonglong2 e) { return (e.x >> 36) | ((e.y & 0xFF) << 28); }
-__device__ __forceinline__ u64 jt_after2(ulonglong2 e) { return (e.y >> 8) & JUMP_NODE_MASK; }
+__device__ __forceinline__ u64 jt_mid(ulonglong2 e) { return (e.y >> 8) & JUMP_NODE_MASK; }
 __device__ __forceinline__ u32 jt_labels(ulonglong2 e) { return u32(e.y >> 44) & 0xFFFF; }
 __device__ __forceinline__ u32 jt_len(ulonglong2 e) { return u32(e.y >> 60); }
-__device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 after2, u32 labels, u32 len)
+__device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 mid, u32 labels, u32 len)
 {
-  return make_ulonglong2(end | (after4 << 36), (after4 >> 28) | (after2 << 8) | (u64(labels) << 44) | (u64(len) << 60));
+  return make_ulonglong2(end | (after4 << 36), (after4 >> 28) | (mid << 8) | (u64(labels) << 44) | (u64(len) << 60));
 }
 
 // PAIR = true: two characters per step through the FLP128 pair blocks whenever the next two pattern
@@ -408,6 +411,8 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
   bool done = true;
   [[maybe_unused]] bool tried = false;     // JUMP: the entry of the current node was examined and does not apply
   [[maybe_unused]] bool no_jump = false;   // JUMP: no entry can apply for the rest of this pattern
+  // JUMP: the two prefixes of a longer chain that an entry offers, {4, 2} or {6, 4} steps (jump_mid = 2 or 6)
+  [[maybe_unused]] const u32 take_hi = (img.jump_mid == 6 ? 6u : 4u), take_lo = (img.jump_mid == 6 ? 4u : 2u);
   [[maybe_unused]] u64 win_code = 0;       // packed pattern window (see below)
   [[maybe_unused]] u32 win_used = ~u32(0), win_bad = 0;      // characters consumed since the window was loaded (~0: no window)
   [[maybe_unused]] u32 force_single = 0;   // PAIR: characters that must be consumed by single steps (replay)
@@ -489,7 +494,9 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
     ulonglong2 entry = make_ulonglong2(0, 0);
     if constexpr(JUMP)
     {
-      jumping = !done && sp == ep && i >= 2 && !tried && !no_jump;   // the last character is a plain step: same cost, no wasted lookup
+      // the last character is a plain step: same cost, no wasted lookup; so are the last two or three where the shortest
+      // prefix an entry offers is 4 (jump_mid = 6): only a whole chain of <= 3 could apply, in front of a step needed anyway
+      jumping = !done && sp == ep && i >= take_lo && !tried && !no_jump;
       entry = img.jump_tab[jumping ? sp : 0];                  // branch-free: all lanes' loads in flight together
     }
     if constexpr(WINDOW)
@@ -677,11 +684,11 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
         u32 usable = (bad != 0 ? u32(__ffs(int(bad)) - 1) >> 1 : 8u);
         usable = (usable < len ? usable : len);
         usable = (usable < i ? usable : u32(i));
-        u32 take = (usable == len ? len : (usable >= 4 ? 4u : (usable >= 2 ? 2u : 0u)));
+        u32 take = (usable == len ? len : (usable >= take_hi ? take_hi : (usable >= take_lo ? take_lo : 0u)));
         if(STATS) { jumps++; }
         if(take > 0)
         {
-          sp = ep = (take == len ? jt_end(entry) : (take == 4 ? jt_after4(entry) : jt_after2(entry)));
+          sp = ep = (take == len ? jt_end(entry) : (take == 4 ? jt_after4(entry) : jt_mid(entry)));
           i -= take; win_used += take; done = (i == 0);
           // A whole chain shorter than JUMP_MAX ended because the node it reaches is not forced: its entry is empty, so
           // step from it instead of looking it up.
@@ -692,7 +699,10 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
         {
           tried = true;                                        // step normally from this node
           // A chain the pattern leaves (or outlasts by one character): the nodes the steps will visit lie
-          // on that same chain, so no later entry can apply either.
+          // on that same chain, so no later entry can apply either.  The same under either jump_mid: a take of 0 with
+          // len > 0 means usable < len and usable < take_lo <= i, so it is the pattern, not its end, that stops short of the
+          // chain -- a character differs from the only label into a forced node within the next take_lo steps, and the
+          // range empties there.
           no_jump = (len > 0);
         }
       }
@@ -886,17 +896,21 @@ __global__ __launch_bounds__(TPB) void k_jump_init(DevImage img, u64 first, ulon
 }
 
 // Doubling: an entry that is full at `have` steps is extended by the entry of the node it reaches; the
-// node it reaches is recorded as the 2-step / 4-step landing point when have is 2 / 4.
-__global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restrict__ in, u64 n, u64 first, u32 have,
+// node it reaches is recorded as the 2-step / 4-step landing point when have is 2 / 4.  The middle slot holds the node
+// after 2 steps through every pass; mid = 6 turns it into the node after 6 steps in the last pass (4 -> 8), which reads
+// the previous pass's buffer, where every slot still is "after 2": 6 steps are the 4 of this entry and the first 2 of the
+// entry of the node they reach, if that one has them, and an entry that ends up shorter than 6 gets a zero slot.
+__global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restrict__ in, u64 n, u64 first, u32 have, u32 mid,
                                                      ulonglong2* __restrict__ out)
 {
   u64 v = first + u64(blockIdx.x) * TPB + threadIdx.x;
   if(v >= n) { return; }
   ulonglong2 e = in[v];
+  const bool to6 = (mid == 6 && have == 4);
   if(jt_len(e) == have)
   {
     const u64 here = jt_end(e);
-    u64 after2 = (have == 2 ? here : jt_after2(e)), after4 = (have == 4 ? here : jt_after4(e));
+    u64 after2 = (have == 2 ? here : jt_mid(e)), after4 = (have == 4 ? here : jt_after4(e));
     u64 end = here; u32 labels = jt_labels(e), len = have;
     ulonglong2 next = in[here];
     if(jt_len(next) > 0)
@@ -905,15 +919,17 @@ __global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restric
       end = jt_end(next); len = have + jt_len(next);
       if(have == 1) { after2 = end; }                        // 1 + 1 steps
     }
+    if(to6) { after2 = (jt_len(next) >= 2 ? jt_mid(next) : 0); }   // 4 + 2 steps
     e = jt_make(end, after4, after2, labels & 0xFFFF, len);
   }
+  else if(to6 && jt_len(e) > 0) { e = jt_make(jt_end(e), jt_after4(e), 0, jt_labels(e), jt_len(e)); }   // len < 4
   out[v] = e;
 }
 
 // The same table without a second buffer: every node walks its own forced chain (at most JUMP_MAX steps) and writes its
 // final entry.  What the doubling leaves in an entry is a function of the chain alone -- len = the number of consecutive
-// forced nodes from v on, capped at 8; the node after len steps; the node after 4 steps when len >= 4 and after 2 steps
-// when len >= 2, zero otherwise; the labels of the len steps; the all-zero entry when v itself is not forced -- so the
+// forced nodes from v on, capped at 8; the node after len steps; the node after 4 steps when len >= 4 and after jump_mid
+// steps when len >= jump_mid, zero otherwise; the labels of the len steps; the all-zero entry when v itself is not forced -- so the
 // two builders write identical bits.  Costs up to 8 dependent LF steps per node against the doubling's 1 + 3 passes; it
 // is what an index takes whose table fits the device but not twice.
 __global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulonglong2* __restrict__ table)
@@ -922,7 +938,7 @@ __global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulon
   stage_tables(img, t);
   u64 v = first + u64(blockIdx.x) * TPB + threadIdx.x;
   if(v >= img.n) { return; }
-  u64 cur = v, after2 = 0, after4 = 0;
+  u64 cur = v, after_mid = 0, after4 = 0;
   u32 labels = 0, len = 0;
   while(len < JUMP_MAX && cur < img.n)
   {
@@ -937,10 +953,10 @@ __global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulon
     cur = bv_rank(img.edges, clampu(t.C[comp] + rank, img.e));         // lf_node() of a node whose only label is comp
     labels |= (comp - 1) << (2 * len);
     len++;
-    if(len == 2) { after2 = cur; }
+    if(len == img.jump_mid) { after_mid = cur; }
     if(len == 4) { after4 = cur; }
   }
-  table[v] = (len > 0 ? jt_make(cur, after4, after2, labels, len) : make_ulonglong2(0, 0));
+  table[v] = (len > 0 ? jt_make(cur, after4, after_mid, labels, len) : make_ulonglong2(0, 0));
 }
 
 // LF_fast (all = 0, comps 1..fast_chars) / LF_all (all = 1, comps 1..sigma-2); src/gcsa.cpp:742-798

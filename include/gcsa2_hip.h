@@ -231,6 +231,14 @@ uint64_t gcsa2_locate_table_bytes(const gcsa2_index* index);
  * second buffer of the table's size (the default where both buffers pass the free-memory test), or one pass of chain
  * walks that needs no second buffer. */
 uint64_t gcsa2_jump_table_bytes(const gcsa2_index* index);
+/* An entry also holds the nodes after 4 and after `mid` steps of its chain, for patterns that end inside it.  mid is 2, or
+ * 6 on an image with pair blocks whose table is larger than the 256 MiB last-level cache: there every lookup is a memory
+ * request, a tail of 6 or 7 characters becomes one lookup instead of two, and a tail of 2 or 3 is left to the pair step.
+ * Ranges are the same either way.  GCSA2_JUMP_MID=2|6 (read at create time; any other value is ignored) overrides the rule.
+ * gcsa2_jump_mid: the value of this image (2 without a table); gcsa2_jump_mid_default: what the rule gives for an image of
+ * `nodes` path nodes with (1) or without (0) pair blocks. */
+int gcsa2_jump_mid(const gcsa2_index* index);
+int gcsa2_jump_mid_default(uint64_t nodes, int pair_blocks);
 /* Bytes of the two-characters-per-step blocks (0 = none).  For every ordered pair of fast characters the
  * composition of two LF steps (gcsa.h:155-162 applied twice) is stored as one rank structure of 128-byte
  * blocks over 192 path nodes each (gcsa2_amd/csrc/layout.hpp "FLP128"): find() then consumes two pattern
