@@ -16,6 +16,9 @@
 //   kernels_mem.hpp     k_mem_*               a MEM finder's count() + locate() per match (vg's seeding), src/gcsa.cpp:802-878
 //   kernels_minimizers.hpp k_minimizers      the (w, k)-minimizers of every read (gcsa2_minimizers_device)
 //                       k_minimizer_seeds     k_kmer_seeds over the selected windows (gcsa2_minimizer_hits_device)
+//   kernels_strands.hpp k_canonical_minimizers the same selection by the smaller hash of a window and its reverse complement
+//                       k_strand_windows      the minimizer CSR as the searched windows of both strands, as 64-bit keys
+//                       k_strand_seeds        k_kmer_seeds over such keys (gcsa2_stranded_minimizer_hits_device)
 //   kernels_windows.hpp k_kmer_windows        GCSA::find + GCSA::count of every k-mer window of every read, per-read sums
 //                       k_kmer_seeds          the same search, emitting the found windows as seed records (gcsa2_kmer_hits_device)
 //                                                                        include/gcsa/gcsa.h:96-110, src/gcsa.cpp:802-809
@@ -36,6 +39,7 @@
 #include "sdsl_writer.hpp"
 #include "../../include/gcsa2_hip.h"
 #include "../../include/gcsa2_hip_chains.h"
+#include "../../include/gcsa2_hip_strands.h"
 
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -52,6 +56,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -65,6 +70,7 @@ using namespace g2;
 #include "kernels_mem.hpp"
 #include "kernels_windows.hpp"
 #include "kernels_minimizers.hpp"
+#include "kernels_strands.hpp"
 #include "kernels_lcp.hpp"
 #include "kernels_submem.hpp"
 #include "kernels_seeds.hpp"
@@ -4995,9 +5001,11 @@ int kmer_windows_core(const gcsa2_index* ix, const uint8_t* d_patterns, const ui
 // run zeroes what it left behind (`prof`, found[spans]) and the area is taken after the owners are on their way; attempts ==
 // 1 (capacity == total): the area first, one run.  One host round trip per run.
 // `mins` (gcsa2_minimizer_hits_device): the windows are those of this list, woff its offsets per read; `stride` is not used.
+// `wins` (gcsa2_stranded_minimizer_hits_device): the windows are the {key, position} entries of this list, woff its offsets per
+// group; the patterns are not read.
 int kmer_seed_search(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
                      const u64* woff, u64 total, u64 capacity, gcsa2_kmer_profile* prof, int attempts, hipStream_t st, SeedEmit& emit, u64& m,
-                     const gcsa2_minimizer* mins = nullptr)
+                     const gcsa2_minimizer* mins = nullptr, const ulonglong2* wins = nullptr)
 {
   const u64 spans = (total + OWNER_SPAN - 1) / OWNER_SPAN;
   static_assert(OWNER_SPAN == 64, "one SeedEmit entry per wavefront of the search");
@@ -5028,7 +5036,12 @@ int kmer_seed_search(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_p
     HIP_TRY(hipMemsetAsync(emit.cursor, 0, sizeof(unsigned long long), st));
     if(rerun) { HIP_TRY(hipMemsetAsync(emit.found + spans, 0, sizeof(u32), st)); }
     if(prof != nullptr) { HIP_TRY(hipMemsetAsync(prof, 0, n_patterns * sizeof(gcsa2_kmer_profile), st)); }
-    if(mins != nullptr)
+    if(wins != nullptr)
+    {
+      if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_strand_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, k, wins, woff, owners, total, prof, emit); }
+      else { hipLaunchKernelGGL((k_strand_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, k, wins, woff, owners, total, prof, emit); }
+    }
+    else if(mins != nullptr)
     {
       if(ix->img.flp != nullptr) { hipLaunchKernelGGL((k_minimizer_seeds<true>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, mins, woff, owners, total, prof, emit); }
       else { hipLaunchKernelGGL((k_minimizer_seeds<false>), grid, dim3(TPB2), 0, st, ix->img, d_patterns, d_offsets, k, mins, woff, owners, total, prof, emit); }
@@ -5150,11 +5163,12 @@ int kmer_hits_checks(const gcsa2_index* ix, u64 k, u64 stride, int over, const u
 // Scratch: per read the window offsets and, if asked for, the profiles (the caller's only once everything fits); per 64
 // windows the owner entry and 16 bytes of SeedEmit; the rest per seed.
 // kmer_hits_found is everything behind the plan of the windows: `total` windows with the offsets `woff` per read, at j stride
-// or, with `mins` (gcsa2_minimizer_hits_device), at the positions of that list.
+// or, with `mins` (gcsa2_minimizer_hits_device), at the positions of that list, or, with `wins`
+// (gcsa2_stranded_minimizer_hits_device), the keys of that list: the "reads" are then its groups.
 int kmer_hits_found(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride,
                     const u64* woff, u64 total, const gcsa2_minimizer* mins, u64 hit_max, int over,
                     gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity, u64* total_seeds,
-                    u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+                    u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st, const ulonglong2* wins = nullptr)
 {
   int rc = GCSA2_OK;
   // no seed: zeroed offsets, the profiles are their window numbers
@@ -5178,7 +5192,7 @@ int kmer_hits_found(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_pa
   SeedEmit emit{};
   u64 m = 0;
   if(d_profiles != nullptr) { HIP_TRY(scratch.get(prof, n_patterns)); }
-  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, std::min(seed_capacity, total), prof, 2, st, emit, m, mins);
+  rc = kmer_seed_search(ix, scratch, d_patterns, d_offsets, n_patterns, k, stride, woff, total, std::min(seed_capacity, total), prof, 2, st, emit, m, mins, wins);
   if(rc != GCSA2_OK) { return rc; }
   if(m > emit.capacity) { scratch.settled = true; return fail(GCSA2_ERR_HIP, "kmer_hits: two runs of the search disagree on the number of seeds"); }
   *total_seeds = m;
@@ -5326,10 +5340,13 @@ int minimizer_hits_checks(const gcsa2_index* ix, u64 k, u64 w, int over, const u
 // scratch), one host round trip for the number of minimizers and of stride-1 windows, then the same pass again placing the
 // records -- into scratch (to_scratch), or into `out` if they fit in `capacity` (else GCSA2_ERR_BUFFER_TOO_SMALL with the
 // offsets complete and no record written).  The stream is idle when this returns a refusal; after the placing pass it is not.
+// Rec: gcsa2_minimizer, or gcsa2_canonical_minimizer for the canonical selection (k_canonical_minimizers).
+template<class Rec>
 int minimizer_select(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w,
-                     u64 hash_seed, u64* moff_or_null, bool to_scratch, gcsa2_minimizer* out, u64 capacity, const char* name, hipStream_t st,
-                     u64*& moff, gcsa2_minimizer*& mins, u64& total)
+                     u64 hash_seed, u64* moff_or_null, bool to_scratch, typename std::common_type<Rec*>::type out, u64 capacity, const char* name,
+                     hipStream_t st, u64*& moff, Rec*& mins, u64& total)
 {
+  constexpr bool CANONICAL = std::is_same<Rec, gcsa2_canonical_minimizer>::value;
   u64 *sizes = nullptr, *windows = nullptr;
   char *scan_tmp = nullptr, *sum_tmp = nullptr;
   moff = moff_or_null;
@@ -5339,8 +5356,16 @@ int minimizer_select(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_p
   HIP_TRY(scratch.get(windows, 1));
   if(moff == nullptr) { HIP_TRY(scratch.get(moff, n_patterns + 1)); }
   const dim3 grid(unsigned(std::min<u64>(n_patterns, u64(1) << 20)));
-  hipLaunchKernelGGL((k_minimizers<false>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed, sizes,
-                     static_cast<const u64*>(nullptr), static_cast<gcsa2_minimizer*>(nullptr));
+  if constexpr(CANONICAL)
+  {
+    hipLaunchKernelGGL((k_canonical_minimizers<false>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed,
+                       sizes, static_cast<const u64*>(nullptr), static_cast<Rec*>(nullptr));
+  }
+  else
+  {
+    hipLaunchKernelGGL((k_minimizers<false>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed, sizes,
+                       static_cast<const u64*>(nullptr), static_cast<Rec*>(nullptr));
+  }
   LAUNCH_CHECK("k_minimizers");
   size_t scan_bytes = 0, sum_bytes = 0;
   hipcub::TransformInputIterator<u64, MiniWindowsOf, hipcub::CountingInputIterator<u64>> per_read(hipcub::CountingInputIterator<u64>(0), MiniWindowsOf{d_offsets, k});
@@ -5360,8 +5385,16 @@ int minimizer_select(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_p
   else if(total > capacity) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer buffer too small"); }
   if(total == 0) { return GCSA2_OK; }
   scratch.settled = false;
-  hipLaunchKernelGGL((k_minimizers<true>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed,
-                     static_cast<u64*>(nullptr), static_cast<const u64*>(moff), mins);
+  if constexpr(CANONICAL)
+  {
+    hipLaunchKernelGGL((k_canonical_minimizers<true>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed,
+                       static_cast<u64*>(nullptr), static_cast<const u64*>(moff), mins);
+  }
+  else
+  {
+    hipLaunchKernelGGL((k_minimizers<true>), grid, dim3(MINI_TPB), 0, st, ix->img, d_patterns, d_offsets, n_patterns, u32(k), u32(w), hash_seed,
+                       static_cast<u64*>(nullptr), static_cast<const u64*>(moff), mins);
+  }
   LAUNCH_CHECK("k_minimizers");
   return GCSA2_OK;
 }
@@ -5382,13 +5415,11 @@ int minimizer_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const 
                          seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
 }
 
-}  // namespace
-
-extern "C" {
-
-int gcsa2_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
-                            uint64_t hash_seed, uint64_t* d_min_offsets, gcsa2_minimizer* d_minimizers, uint64_t capacity, uint64_t* total,
-                            void* stream)
+// gcsa2_minimizers_device and gcsa2_canonical_minimizers_device (Rec, as minimizer_select)
+template<class Rec>
+int minimizers_device_form(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                           uint64_t hash_seed, uint64_t* d_min_offsets, Rec* d_minimizers, uint64_t capacity, uint64_t* total, void* stream,
+                           const char* entry)
 {
   int rc = minimizers_checks(ix, k, w, total);
   if(rc != GCSA2_OK) { return rc; }
@@ -5410,7 +5441,7 @@ int gcsa2_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, co
   }
   Scratch scratch(ix, st);
   u64* moff = nullptr;
-  gcsa2_minimizer* mins = nullptr;
+  Rec* mins = nullptr;
   u64 found = 0;
   rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, d_min_offsets, false, d_minimizers, capacity, "minimizers", st,
                         moff, mins, found);
@@ -5419,14 +5450,15 @@ int gcsa2_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, co
   HIP_TRY(hipStreamSynchronize(st));
   scratch.settled = true;
   return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizers_device: ") + e.what()); }
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(entry) + ": " + e.what()); }
 }
 
 // The host form.  The number of minimizers of a piece (for_read_pieces) is not known before it ran, so every piece keeps its
 // offsets and records in host memory and the caller's arrays are put together in read order at the end; the offsets are
 // complete and *total is written whether the records fit or not.
-int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
-                           uint64_t hash_seed, uint64_t* min_offsets, gcsa2_minimizer* minimizers, uint64_t capacity, uint64_t* total)
+template<class Rec>
+int minimizers_batch_form(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                          uint64_t hash_seed, uint64_t* min_offsets, Rec* minimizers, uint64_t capacity, uint64_t* total, const char* entry)
 {
   int rc = minimizers_checks(ix, k, w, total);
   if(rc != GCSA2_OK) { return rc; }
@@ -5443,7 +5475,7 @@ int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const
   g_error.clear();
   if(host_windows(offsets, n_patterns, k, 1) >= (u64(1) << 32)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizers: 2^32 or more windows in one call; split the batch"); }
   const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
-  struct Piece { std::vector<u64> off; std::vector<gcsa2_minimizer> mins; };
+  struct Piece { std::vector<u64> off; std::vector<Rec> mins; };
   std::vector<Piece> done(cut.size() - 1);
   rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
   {
@@ -5452,13 +5484,13 @@ int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const
     if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
     Scratch scratch(ix, p.stream);
     u64 *moff = nullptr, found = 0;
-    gcsa2_minimizer* mins = nullptr;
+    Rec* mins = nullptr;
     const int piece_rc = minimizer_select(ix, scratch, d_pat.p, d_off.p, p.count, k, w, hash_seed, nullptr, true, nullptr, 0, "minimizers", p.stream,
                                           moff, mins, found);
     if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
     piece.off.resize(p.count + 1); piece.mins.resize(found);
     hipError_t e = hipMemcpyAsync(piece.off.data(), moff, (p.count + 1) * sizeof(u64), hipMemcpyDeviceToHost, p.stream);
-    if(e == hipSuccess && found > 0) { e = hipMemcpyAsync(piece.mins.data(), mins, found * sizeof(gcsa2_minimizer), hipMemcpyDeviceToHost, p.stream); }
+    if(e == hipSuccess && found > 0) { e = hipMemcpyAsync(piece.mins.data(), mins, found * sizeof(Rec), hipMemcpyDeviceToHost, p.stream); }
     if(e == hipSuccess) { e = hipStreamSynchronize(p.stream); }
     if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
     scratch.settled = true;
@@ -5477,11 +5509,29 @@ int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const
   base = 0;
   for(const Piece& piece : done)
   {
-    if(!piece.mins.empty()) { std::memcpy(minimizers + base, piece.mins.data(), piece.mins.size() * sizeof(gcsa2_minimizer)); }
+    if(!piece.mins.empty()) { std::memcpy(minimizers + base, piece.mins.data(), piece.mins.size() * sizeof(Rec)); }
     base += piece.mins.size();
   }
   return GCSA2_OK;
-  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizers_batch: ") + e.what()); }
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string(entry) + ": " + e.what()); }
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                            uint64_t hash_seed, uint64_t* d_min_offsets, gcsa2_minimizer* d_minimizers, uint64_t capacity, uint64_t* total,
+                            void* stream)
+{
+  return minimizers_device_form(ix, d_patterns, d_offsets, n_patterns, k, w, hash_seed, d_min_offsets, d_minimizers, capacity, total, stream,
+                                "gcsa2_minimizers_device");
+}
+
+int gcsa2_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                           uint64_t hash_seed, uint64_t* min_offsets, gcsa2_minimizer* minimizers, uint64_t capacity, uint64_t* total)
+{
+  return minimizers_batch_form(ix, patterns, offsets, n_patterns, k, w, hash_seed, min_offsets, minimizers, capacity, total, "gcsa2_minimizers_batch");
 }
 
 int gcsa2_minimizer_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
@@ -5553,6 +5603,163 @@ int gcsa2_minimizer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, c
   return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, sizeof(gcsa2_kmer_profile), profiles, seed_offsets, seeds, seed_capacity,
                            total_seeds, hit_offsets, hits, hit_capacity, total_hits);
   } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_minimizer_hits_batch: ") + e.what()); }
+}
+
+}  // extern "C"
+
+// ==== stranded minimizer seeds: canonical minimizers and their hits on both strands (gcsa2_hip_strands.h, kernels_strands.hpp) ====
+namespace {
+
+// what both forms of the hits refuse before any device is touched, then the components the hits need
+int stranded_hits_checks(const gcsa2_index* ix, u64 k, u64 w, int strands, int over, const u64* total_seeds, const u64* total_hits)
+{
+  const int rc = minimizers_checks(ix, k, w, total_seeds);
+  if(rc != GCSA2_OK) { return rc; }
+  if(total_hits == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "null total pointer"); }
+  if(strands < GCSA2_STRAND_FORWARD || strands > GCSA2_STRAND_BOTH)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "stranded_minimizer_hits: strands must be GCSA2_STRAND_FORWARD, GCSA2_STRAND_REVERSE or GCSA2_STRAND_BOTH");
+  }
+  if(over != GCSA2_MEM_OVER_SKIP && over != GCSA2_MEM_OVER_SAMPLE)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "stranded_minimizer_hits: unknown over-cap policy (GCSA2_MEM_OVER_SKIP or GCSA2_MEM_OVER_SAMPLE)");
+  }
+  if((strands & GCSA2_STRAND_REVERSE) != 0 && ix->img.sigma < 6)
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "stranded_minimizer_hits: the reverse strand needs an alphabet with four codes (sigma >= 6)");
+  }
+  return locate_checks(ix, 0);
+}
+
+// gcsa2_stranded_minimizer_hits_device after its argument checks (0 < n_patterns < 2^31): the canonical selection into scratch,
+// the searched windows of the strands asked for as keys in group order (k_strand_windows), then what gcsa2_kmer_hits_device
+// does behind its window plan with the 2 n_patterns groups as the reads and k_strand_seeds as the search.
+int stranded_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
+                       int strands, u64 hit_max, int over, gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity,
+                       u64* total_seeds, u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *moff = nullptr, total = 0;
+  gcsa2_canonical_minimizer* mins = nullptr;
+  const int rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, "stranded_minimizer_hits", st,
+                                  moff, mins, total);
+  if(rc != GCSA2_OK) { return rc; }
+  const u64 searched = (strands == GCSA2_STRAND_BOTH ? 2 : 1) * total;
+  if(searched >= (u64(1) << 32))
+  {
+    HIP_TRY(hipStreamSynchronize(st));                       // the placing pass
+    scratch.settled = true;
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "stranded_minimizer_hits: 2^32 or more searched windows in one call; split the batch");
+  }
+  u64* goff = nullptr;
+  ulonglong2* wins = nullptr;
+  HIP_TRY(scratch.get(goff, 2 * n_patterns + 1));
+  HIP_TRY(scratch.get(wins, searched));
+  if(searched > 0)
+  {
+    scratch.settled = false;
+    hipLaunchKernelGGL(k_strand_windows, dim3(grid_for((n_patterns + 1) * STRAND_LANES)), dim3(TPB), 0, st, d_offsets, n_patterns, u32(k), moff, mins,
+                       u32(strands), goff, wins);
+    LAUNCH_CHECK("k_strand_windows");
+  }
+  return kmer_hits_found(ix, scratch, nullptr, nullptr, 2 * n_patterns, k, 1, goff, searched, nullptr, hit_max, over, d_profiles, d_seed_offsets, d_seeds,
+                         seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st, wins);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_canonical_minimizers_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                                      uint64_t w, uint64_t hash_seed, uint64_t* d_min_offsets, gcsa2_canonical_minimizer* d_minimizers,
+                                      uint64_t capacity, uint64_t* total, void* stream)
+{
+  return minimizers_device_form(ix, d_patterns, d_offsets, n_patterns, k, w, hash_seed, d_min_offsets, d_minimizers, capacity, total, stream,
+                                "gcsa2_canonical_minimizers_device");
+}
+
+int gcsa2_canonical_minimizers_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                     uint64_t hash_seed, uint64_t* min_offsets, gcsa2_canonical_minimizer* minimizers, uint64_t capacity,
+                                     uint64_t* total)
+{
+  return minimizers_batch_form(ix, patterns, offsets, n_patterns, k, w, hash_seed, min_offsets, minimizers, capacity, total,
+                               "gcsa2_canonical_minimizers_batch");
+}
+
+int gcsa2_stranded_minimizer_hits_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k,
+                                         uint64_t w, uint64_t hash_seed, int strands, uint64_t hit_max, int over, gcsa2_kmer_profile* d_profiles,
+                                         uint64_t* d_seed_offsets, gcsa2_mem* d_seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                                         uint64_t* d_hit_offsets, uint64_t* d_hits, uint64_t hit_capacity, uint64_t* total_hits, void* stream)
+{
+  int rc = stranded_hits_checks(ix, k, w, strands, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(d_seed_offsets == nullptr || d_hit_offsets == nullptr || (n_patterns > 0 && d_offsets == nullptr) || (d_seeds == nullptr && seed_capacity > 0) ||
+     (d_hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 31)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "stranded_minimizer_hits: 2^31 or more reads in one call; split the batch"); }
+  try {   // no C++ exception may cross the C boundary
+  DeviceGuard guard(ix->device);
+  g_error.clear();
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if(n_patterns == 0)
+  {
+    HIP_TRY(hipMemsetAsync(d_seed_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(u64), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return GCSA2_OK;
+  }
+  return stranded_hits_core(ix, d_patterns, d_offsets, n_patterns, k, w, hash_seed, strands, hit_max, over, d_profiles, d_seed_offsets, d_seeds,
+                            seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_stranded_minimizer_hits_device: ") + e.what()); }
+}
+
+// The host form (seed_pieces_batch with two groups per read), as gcsa2_minimizer_hits_batch: the groups are per read, so the
+// cut changes nothing.
+int gcsa2_stranded_minimizer_hits_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k,
+                                        uint64_t w, uint64_t hash_seed, int strands, uint64_t hit_max, int over, gcsa2_kmer_profile* profiles,
+                                        uint64_t* seed_offsets, gcsa2_mem* seeds, uint64_t seed_capacity, uint64_t* total_seeds,
+                                        uint64_t* hit_offsets, uint64_t* hits, uint64_t hit_capacity, uint64_t* total_hits)
+{
+  int rc = stranded_hits_checks(ix, k, w, strands, over, total_seeds, total_hits);
+  if(rc != GCSA2_OK) { return rc; }
+  *total_seeds = 0;
+  *total_hits = 0;
+  if(seed_offsets == nullptr || hit_offsets == nullptr || (n_patterns > 0 && offsets == nullptr) || (seeds == nullptr && seed_capacity > 0) ||
+     (hits == nullptr && hit_capacity > 0))
+  {
+    return fail(GCSA2_ERR_INVALID_ARGUMENT, "null buffer");
+  }
+  if(n_patterns >= (u64(1) << 31)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "stranded_minimizer_hits: 2^31 or more reads in one call; split the batch"); }
+  if(n_patterns == 0) { seed_offsets[0] = 0; hit_offsets[0] = 0; return GCSA2_OK; }
+  rc = reads_ok(patterns, offsets, n_patterns, nullptr);
+  if(rc != GCSA2_OK) { return rc; }
+  try {   // no C++ exception may cross the C boundary
+  g_error.clear();
+  if(host_windows(offsets, n_patterns, k, 1) >= (u64(1) << 32))
+  {
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "stranded_minimizer_hits: 2^32 or more windows in one call; split the batch");
+  }
+  const u64 per = (strands == GCSA2_STRAND_BOTH ? 2 : 1);
+  // several pieces: room for every span's minimizer on the strands asked for, and an estimate of the hits
+  auto estimate = [&](const ReadPiece& p) -> std::pair<u64, u64>
+  {
+    const u64 windows = per * host_windows(p.local, p.count, k, 1);
+    if(p.pieces == 1) { return {std::min(seed_capacity, windows), hit_capacity}; }
+    return {windows, 4 * windows};
+  };
+  auto run = [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, u8* d_prof, u64* d_seed_off, gcsa2_mem* d_seeds, u64 rm, u64* m, u64* d_hit_off,
+                 u64* d_hits, u64 rh, u64* h) -> int
+  {
+    return gcsa2_stranded_minimizer_hits_device(ix, d_pat, d_off, p.count, k, w, hash_seed, strands, hit_max, over,
+                                                reinterpret_cast<gcsa2_kmer_profile*>(d_prof), d_seed_off, d_seeds, rm, m, d_hit_off, d_hits, rh, h, p.stream);
+  };
+  return seed_pieces_batch(ix, patterns, offsets, n_patterns, estimate, run, sizeof(gcsa2_kmer_profile), profiles, seed_offsets, seeds, seed_capacity,
+                           total_seeds, hit_offsets, hits, hit_capacity, total_hits, 2);
+  } catch(const std::exception& e) { return fail(GCSA2_ERR_OUT_OF_MEMORY, std::string("gcsa2_stranded_minimizer_hits_batch: ") + e.what()); }
 }
 
 }  // extern "C"

@@ -198,10 +198,12 @@ inline bool upload_reads(const ReadPiece& piece, const uint8_t* patterns, DBuf<u
 //   run(piece, d_pat, d_off, d_per_read, d_seed_off, d_seeds, rm, &m, d_hit_off, d_hits, rh, &h) -> status
 //                                   the device form on piece.stream
 // and, if the call has one, an output of per_read_bytes per read (per_read, null: none), copied to its reads' place.
+// `groups`: the seed CSR and the per-read output have this many consecutive entries per read (2: a read's two strands,
+// gcsa2_stranded_minimizer_hits_batch); per_read_bytes is then the size of one entry.
 template<class Estimate, class Run>
 int seed_pieces_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n, Estimate estimate, Run run, u64 per_read_bytes,
                       void* per_read, uint64_t* seed_offsets, gcsa2_mem* seeds, u64 seed_capacity, u64* total_seeds, uint64_t* hit_offsets,
-                      uint64_t* hits, u64 hit_capacity, u64* total_hits)
+                      uint64_t* hits, u64 hit_capacity, u64* total_hits, u64 groups = 1)
 {
   const std::vector<u64> cut = read_cut(ix, offsets, n);
   struct Piece { u64 m = 0, h = 0; std::vector<u64> seed_off, hit_off, hits; std::vector<gcsa2_mem> seeds; };
@@ -211,8 +213,8 @@ int seed_pieces_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint
     Piece& piece = done[p.c];
     DBuf<u8> d_pat, d_per_read; DBuf<u64> d_off, d_seed_off, d_hit_off, d_hits; DBuf<gcsa2_mem> d_seeds;
     if(!upload_reads(p, patterns, d_pat, d_off, out)) { return false; }
-    hipError_t e = d_seed_off.alloc(p.count + 1);
-    if(e == hipSuccess && per_read != nullptr) { e = d_per_read.alloc(p.count * per_read_bytes); }
+    hipError_t e = d_seed_off.alloc(groups * p.count + 1);
+    if(e == hipSuccess && per_read != nullptr) { e = d_per_read.alloc(groups * p.count * per_read_bytes); }
     if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
     std::pair<u64, u64> room = estimate(p);
     u64 &rm = room.first, &rh = room.second;
@@ -230,12 +232,12 @@ int seed_pieces_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint
     }
     if(e != hipSuccess) { out.set(e == hipErrorOutOfMemory ? GCSA2_ERR_OUT_OF_MEMORY : GCSA2_ERR_HIP, std::string("buffers of a piece: ") + hipGetErrorString(e)); return false; }
     if(piece_rc != GCSA2_OK) { out.set(piece_rc, g_error); return false; }
-    piece.seed_off.resize(p.count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
-    e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (p.count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
+    piece.seed_off.resize(groups * p.count + 1); piece.seeds.resize(piece.m); piece.hit_off.resize(piece.m + 1); piece.hits.resize(piece.h);
+    e = hipMemcpy(piece.seed_off.data(), d_seed_off.p, (groups * p.count + 1) * sizeof(u64), hipMemcpyDeviceToHost);
     if(e == hipSuccess && piece.m > 0) { e = hipMemcpy(piece.seeds.data(), d_seeds.p, piece.m * sizeof(gcsa2_mem), hipMemcpyDeviceToHost); }
     if(e == hipSuccess) { e = hipMemcpy(piece.hit_off.data(), d_hit_off.p, (piece.m + 1) * sizeof(u64), hipMemcpyDeviceToHost); }
     if(e == hipSuccess && piece.h > 0) { e = hipMemcpy(piece.hits.data(), d_hits.p, piece.h * sizeof(u64), hipMemcpyDeviceToHost); }
-    if(e == hipSuccess && per_read != nullptr) { e = hipMemcpy(static_cast<u8*>(per_read) + p.b * per_read_bytes, d_per_read.p, p.count * per_read_bytes, hipMemcpyDeviceToHost); }
+    if(e == hipSuccess && per_read != nullptr) { e = hipMemcpy(static_cast<u8*>(per_read) + groups * p.b * per_read_bytes, d_per_read.p, groups * p.count * per_read_bytes, hipMemcpyDeviceToHost); }
     if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
     return true;
   });
@@ -250,7 +252,7 @@ int seed_pieces_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint
   for(u64 c = 0; c + 1 < cut.size(); c++)
   {
     const Piece& piece = done[c];
-    const u64 b = cut[c], count = cut[c + 1] - b;
+    const u64 b = groups * cut[c], count = groups * (cut[c + 1] - cut[c]);
     for(u64 i = 0; i <= count; i++) { seed_offsets[b + i] = piece.seed_off[i] + mbase; }
     if(piece.m > 0) { std::memcpy(seeds + mbase, piece.seeds.data(), piece.m * sizeof(gcsa2_mem)); }
     for(u64 i = 0; i <= piece.m; i++) { hit_offsets[mbase + i] = piece.hit_off[i] + hbase; }

@@ -67,107 +67,15 @@ __device__ __forceinline__ u64 mini_key(u64 a, u64 b, u32 at, u32 k)
 // PLACE == false: sizes[q] = the read's number of minimizers (entry n_patterns: the scan's closing zero).  PLACE == true: the
 // same walk again, records written from min_offsets[q] on.  (The first form also added every read's number of windows to one
 // global counter: a million atomics on one address took 10 of the counting pass's 12 ms; profiles/minimizer_hits.md.)
+// The body is kernels_minimizers_body.hpp, which k_canonical_minimizers (kernels_strands.hpp) shares.
 template<bool PLACE>
 __global__ __launch_bounds__(MINI_TPB) void k_minimizers(DevImage img, const u8* __restrict__ patterns, const u64* __restrict__ offsets, u64 n_patterns,
                                                          u32 k, u32 w, u64 hash_seed, u64* __restrict__ sizes, const u64* __restrict__ min_offsets,
                                                          gcsa2_minimizer* __restrict__ recs)
 {
-  __shared__ u8 c2c[256];
-  __shared__ u64 table_hash[2 * MINI_TILE];
-  __shared__ u32 table_at[2 * MINI_TILE];
-  __shared__ u32 marks[4];
-  const u32 lane = threadIdx.x;
-#pragma unroll
-  for(u32 c = 0; c < 256; c += MINI_TPB) { c2c[c + lane] = img.char2comp[c + lane]; }
-  __syncthreads();
-  const u32 limit = (img.sigma >= 3 ? (img.sigma - 2 < 4 ? u32(img.sigma - 2) : 4u) : 0u);     // codes 0 .. limit - 1
-  const u32 need = MINI_TILE + (w - 1) + (k - 1);            // characters of a tile
-  const u64 kmask = (u64(1) << k) - 1;                       // k <= 32
-  const u64 below = (u64(1) << lane) - 1;
-  if(!PLACE && blockIdx.x == 0 && lane == 0) { sizes[n_patterns] = 0; }
-
-  for(u64 q = blockIdx.x; q < n_patterns; q += gridDim.x)
-  {
-    const u64 begin = offsets[q], len = offsets[q + 1] - begin;
-    const u64 W = (len >= k ? len - k + 1 : 0);
-    const u64 out = (PLACE ? min_offsets[q] : 0);
-    u64 count = 0, carry = 0;
-    bool prev_valid = false;                                 // window base - 1
-    for(u64 base = 0; base < W; base += MINI_TILE)
-    {
-      // 1. the tile's characters as five code words and three words of bad bits
-      u64 bad[3], word[5];
-#pragma unroll
-      for(u32 r = 0; r < 3; r++)
-      {
-        const u32 c = r * 64 + lane;
-        const bool there = c < need && base + c < len;
-        const u32 code = (there ? u32(c2c[patterns[begin + base + c]]) - 1 : ~u32(0));
-        const bool good = code < limit;
-        bad[r] = __ballot(!good);
-        const u64 plane0 = __ballot(good && (code & 1) != 0), plane1 = __ballot(good && (code & 2) != 0);
-        word[2 * r] = mini_spread(__brev(u32(plane0))) | (mini_spread(__brev(u32(plane1))) << 1);
-        if(r < 2) { word[2 * r + 1] = mini_spread(__brev(u32(plane0 >> 32))) | (mini_spread(__brev(u32(plane1 >> 32))) << 1); }
-      }
-      // 2. hash and validity of the lane's window and of its halo window
-      const bool upper = lane >= 32;
-      const u32 at = lane & 31;
-      const u64 key_main = mini_key(upper ? word[1] : word[0], upper ? word[2] : word[1], at, k);
-      const u64 key_halo = mini_key(upper ? word[3] : word[2], upper ? word[4] : word[3], at, k);
-      const u64 hash_main = mini_mix64(key_main ^ hash_seed), hash_halo = mini_mix64(key_halo ^ hash_seed);
-      const u64 valid_lo = __ballot((mini_bits(bad[0], bad[1], lane) & kmask) == 0);
-      const u64 valid_hi = __ballot(lane + 1 < w && (mini_bits(bad[1], bad[2], lane) & kmask) == 0);
-      // 3. the span that starts at the lane's window
-      const u64 from_here = mini_bits(valid_lo, valid_hi, lane);
-      u64 invalid = ~from_here;
-      if(w < 64) { invalid |= u64(1) << w; }
-      const u32 span = (invalid != 0 ? u32(__ffsll((unsigned long long)invalid)) - 1 : 64u);     // valid windows from here on, at most w
-      const bool prev = (lane == 0 ? prev_valid : ((valid_lo >> (lane - 1)) & 1) != 0);
-      const bool want = (from_here & 1) != 0 && (span == w || !prev);
-      const u32 level = (want ? 31 - u32(__clz(int(span))) : ~u32(0));
-      // 4. the sparse table, level by level in place
-      __syncthreads();                                       // the previous tile has read its table and marks
-      table_hash[lane] = hash_main; table_at[lane] = lane;
-      table_hash[MINI_TILE + lane] = hash_halo; table_at[MINI_TILE + lane] = MINI_TILE + lane;
-      if(lane < 4) { marks[lane] = 0; }
-      __syncthreads();
-      u32 best = 0;
-      for(u32 j = 0; ; j++)
-      {
-        const u32 step = u32(1) << j;
-        if(level == j)
-        {
-          const u32 right = lane + span - step;                // < 127: the span ends inside the halo
-          const u64 a = table_hash[lane], b = table_hash[right];
-          best = (a <= b ? table_at[lane] : table_at[right]);
-        }
-        if(2 * step > w) { break; }                            // no span needs a higher level
-        const u32 hi = MINI_TILE + lane;
-        const bool has = hi + step < 2 * MINI_TILE;            // entries without a right half are never asked for
-        const u64 x0 = table_hash[lane], y0 = table_hash[lane + step];
-        const u32 j0 = table_at[lane + step];
-        const u64 x1 = table_hash[hi], y1 = (has ? table_hash[hi + step] : ~u64(0));
-        const u32 j1 = (has ? table_at[hi + step] : 0);
-        __syncthreads();
-        if(y0 < x0) { table_hash[lane] = y0; table_at[lane] = j0; }
-        if(has && y1 < x1) { table_hash[hi] = y1; table_at[hi] = j1; }
-        __syncthreads();
-      }
-      // 5. the selected windows: bits 0..63 are final, the rest goes to the next tile
-      if(want) { atomicOr(&marks[best >> 5], u32(1) << (best & 31)); }
-      __syncthreads();
-      const u64 final_bits = (u64(marks[0]) | (u64(marks[1]) << 32)) | carry;
-      carry = u64(marks[2]) | (u64(marks[3]) << 32);
-      prev_valid = (valid_lo >> 63) != 0;
-      if(PLACE && ((final_bits >> lane) & 1) != 0)
-      {
-        const u64 to = out + count + u64(__popcll(final_bits & below));
-        recs[to].position = base + lane; recs[to].hash = hash_main;
-      }
-      count += u64(__popcll(final_bits));
-    }
-    if(!PLACE && lane == 0) { sizes[q] = count; }
-  }
+#define MINI_CANONICAL 0
+#include "kernels_minimizers_body.hpp"
+#undef MINI_CANONICAL
 }
 
 // the stride-1 windows of read q, for the sum that the limit of a call is checked against

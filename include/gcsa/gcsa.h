@@ -14,6 +14,7 @@
 #include "files.h"
 #include "support.h"
 #include "../gcsa2_hip_chains.h"
+#include "../gcsa2_hip_strands.h"
 
 namespace gcsa
 {
@@ -379,6 +380,69 @@ public:
         continue;
       }
       check(rc, "GCSA::minimizer_hits_batch()");
+      break;
+    }
+    seeds.resize(total_seeds);
+    hit_offsets.resize(total_seeds + 1);
+    hits.resize(total_hits);
+  }
+
+  // The canonical (w, k)-minimizers of every read (gcsa2_canonical_minimizers_batch, gcsa2_hip_strands.h): minimizers() with the
+  // smaller one of the hashes of a window and of its reverse complement as the window's hash, so that a read and its reverse
+  // complement select the same k-mers; records {position, hash, key, strand}.
+  void canonical_minimizers(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                            size_type hash_seed, std::vector<size_type>& min_offsets, std::vector<gcsa2_canonical_minimizer>& minimizers) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    min_offsets.assign(np + 1, 0);
+    minimizers.clear();
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total = 0;
+    for(int attempt = 0; attempt < 2; attempt++)           // the first call sizes the records, unless there are none
+    {
+      const int rc = gcsa2_canonical_minimizers_batch(handle, patterns.empty() ? &dummy : patterns.data(),
+                                                      offsets.empty() ? &dummy_offset : offsets.data(), np, k, w, hash_seed, min_offsets.data(),
+                                                      minimizers.data(), minimizers.size(), &total);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && total > minimizers.size())
+      {
+        minimizers.assign(total, gcsa2_canonical_minimizer());
+        continue;
+      }
+      check(rc, "GCSA::canonical_minimizers()");
+      break;
+    }
+    minimizers.resize(total);
+  }
+
+  // minimizer_hits_batch over the canonical minimizers, on both strands (gcsa2_stranded_minimizer_hits_batch): two groups of seeds
+  // per read, [seed_offsets[2q], seed_offsets[2q + 1]) the minimizers of read q found as written, [seed_offsets[2q + 1],
+  // seed_offsets[2q + 2]) the same windows found in its reverse complement, in that read's coordinates.  strands:
+  // GCSA2_STRAND_FORWARD, GCSA2_STRAND_REVERSE or GCSA2_STRAND_BOTH; the groups of a strand not asked for are empty.
+  void stranded_minimizer_hits_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                                     size_type hash_seed, int strands, size_type hit_max, bool sample, std::vector<size_type>& seed_offsets,
+                                     std::vector<gcsa2_mem>& seeds, std::vector<size_type>& hit_offsets, std::vector<node_type>& hits) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    seed_offsets.assign(2 * np + 1, 0);
+    seeds.clear();
+    hits.clear();
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0, total_seeds = 0, total_hits = 0;
+    for(int attempt = 0; attempt < 2; attempt++)           // the first call sizes the buffers, unless nothing is found
+    {
+      hit_offsets.assign(seeds.size() + 1, 0);
+      const int rc = gcsa2_stranded_minimizer_hits_batch(handle, patterns.empty() ? &dummy : patterns.data(),
+                                                         offsets.empty() ? &dummy_offset : offsets.data(), np, k, w, hash_seed, strands, hit_max,
+                                                         sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, nullptr, seed_offsets.data(),
+                                                         seeds.data(), seeds.size(), &total_seeds, hit_offsets.data(), hits.data(), hits.size(),
+                                                         &total_hits);
+      if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && attempt == 0 && (total_seeds > seeds.size() || total_hits > hits.size()))
+      {
+        seeds.assign(total_seeds, gcsa2_mem());
+        hits.assign(total_hits, 0);
+        continue;
+      }
+      check(rc, "GCSA::stranded_minimizer_hits_batch()");
       break;
     }
     seeds.resize(total_seeds);

@@ -782,7 +782,8 @@ int gcsa2_kmer_hits_batch(const gcsa2_index* index, const uint8_t* patterns, con
  * twice (count, scan, place).  The search is the kernel of gcsa2_kmer_hits_device over the list of selected positions.
  * Device scratch: per read 16 bytes, per minimizer 16 bytes, then that of gcsa2_kmer_hits_device with the minimizers as the windows.
  *
- * Out of scope: canonical (both-strand) minimizers, syncmers, w > 64, k > 32, and minimizer forms of the support and class calls. */
+ * Canonical (both-strand) minimizers and their hits on both strands: gcsa2_hip_strands.h.
+ * Out of scope: syncmers, w > 64, k > 32, and minimizer forms of the support and class calls. */
 #define GCSA2_MINIMIZER_MAX_K 32
 #define GCSA2_MINIMIZER_MAX_W 64
 typedef struct gcsa2_minimizer { uint64_t position, hash; } gcsa2_minimizer;

@@ -9,6 +9,7 @@
 #define GCSA2_HIP_GCSA_HPP
 
 #include "../gcsa2_hip_chains.h"
+#include "../gcsa2_hip_strands.h"
 #include "../gcsa/utils.h"
 #include "../gcsa/files.h"
 #include "../gcsa/support.h"
