@@ -51,7 +51,7 @@ EXPORTS = [
     "gcsa2_size", "gcsa2_edge_count", "gcsa2_order", "gcsa2_sample_count", "gcsa2_sample_bits",
     "gcsa2_device", "gcsa2_device_bytes", "gcsa2_block_bits",
     "gcsa2_find_batch", "gcsa2_find_batch_packed", "gcsa2_find_packed_device", "gcsa2_find_device", "gcsa2_find_stats_device", "gcsa2_find_device_variant",
-    "gcsa2_find_block_bytes", "gcsa2_kmer_table_k", "gcsa2_locate_table_bytes", "gcsa2_jump_table_bytes", "gcsa2_jump_mid", "gcsa2_jump_mid_default", "gcsa2_pair_block_bytes", "gcsa2_lf_batch", "gcsa2_lf_device",
+    "gcsa2_find_block_bytes", "gcsa2_kmer_table_k", "gcsa2_locate_table_bytes", "gcsa2_jump_table_bytes", "gcsa2_jump_mid", "gcsa2_jump_mid_default", "gcsa2_jump_branch", "gcsa2_jump_branch_default", "gcsa2_pair_block_bytes", "gcsa2_lf_batch", "gcsa2_lf_device",
     "gcsa2_lf_node_batch", "gcsa2_char_range", "gcsa2_lf_all_batch",
     "gcsa2_count_batch", "gcsa2_count_device",
     "gcsa2_locate_run", "gcsa2_locate_fetch", "gcsa2_locate_discard", "gcsa2_locate_device", "gcsa2_locate_into",
@@ -129,6 +129,8 @@ def load_library():
         getattr(L, name).argtypes = [vp]
     L.gcsa2_jump_mid.argtypes = [vp]
     L.gcsa2_jump_mid_default.argtypes = [u64, i32]
+    L.gcsa2_jump_branch.argtypes = [vp]
+    L.gcsa2_jump_branch_default.argtypes = [u64, i32]
     L.gcsa2_device.argtypes = [vp]
     L.gcsa2_find_batch.argtypes = [vp, u8p, u64p, u64, u64p]
     L.gcsa2_find_device.argtypes = [vp, vp, vp, u64, vp, vp]
@@ -277,6 +279,12 @@ def jump_mid_default(nodes, pair_blocks):
     """The jump_mid that index creation chooses for an image of `nodes` path nodes with or without pair blocks, when
     GCSA2_JUMP_MID does not override it (gcsa2_jump_mid_default)."""
     return int(load_library().gcsa2_jump_mid_default(int(nodes), 1 if pair_blocks else 0))
+
+
+def jump_branch_default(nodes, pair_blocks):
+    """1 when index creation writes branch records into the jump table of an image of `nodes` path nodes with or without
+    pair blocks, when GCSA2_JUMP_BRANCH does not override it (gcsa2_jump_branch_default)."""
+    return int(load_library().gcsa2_jump_branch_default(int(nodes), 1 if pair_blocks else 0))
 
 
 def _p64(a):
@@ -482,6 +490,10 @@ class GCSA(ChainCalls, StrandCalls):
     def jump_mid(self):
         """Steps behind the middle node slot of this image's jump entries, 2 or 6 (gcsa2_jump_mid)."""
         return int(self._L.gcsa2_jump_mid(self._h))
+
+    def jump_branch(self):
+        """1 when this image's jump table holds branch records, else 0 (gcsa2_jump_branch)."""
+        return int(self._L.gcsa2_jump_branch(self._h))
 
     def set_tables(self, pair_blocks=-1, kmer_k=-1, locate_table=-1):
         """Drop (0) / build (1) / leave (-1) the pair blocks and the locate table, resize the k-mer seed table (0 drops it):

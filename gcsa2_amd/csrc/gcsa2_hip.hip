@@ -218,6 +218,9 @@ inline bool jump_table_fits(u64 bytes, u64 free_bytes, u64 total_bytes) { return
 // characters in one request.  Everywhere else the entry keeps the node after 2 steps.
 constexpr u64 LAST_LEVEL_CACHE_BYTES = u64(256) << 20;
 inline u32 jump_mid_default(u64 nodes, bool pair_blocks) { return pair_blocks && nodes * sizeof(ulonglong2) > LAST_LEVEL_CACHE_BYTES ? 6 : 2; }
+// Branch records (DevImage::jump_branch) save a block fetch at a two-label node for a lookup that lands on it: a trade of
+// requests, which pays under the same rule, and they need the two free slots that only jump_mid = 6 leaves in a short entry.
+inline bool jump_branch_default(u64 nodes, bool pair_blocks) { return jump_mid_default(nodes, pair_blocks) == 6; }
 
 inline void launch_walk(const gcsa2_index* ix, const u64* d_ranges, u64 nq, const u64* node_off, const u64* raw_off,
                         u64 total_nodes, u64* values, u64* owners, hipStream_t stream);
@@ -1139,12 +1142,15 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
   // (1 -> 2 -> 4 -> 8 steps) through a second buffer that is released afterwards where both buffers pass the
   // free-memory test, otherwise one pass of chain walks into the table itself (k_jump_walk); GCSA2_JUMP_BUILD=double|walk
   // forces one of them (tests).  A table that cannot be had is left out without an error.  The middle slot of its entries
-  // holds the node after jump_mid steps: jump_mid_default(), or GCSA2_JUMP_MID=2|6 (any other value is ignored).
-  ix->img.jump_tab = nullptr; ix->img.jump_mid = 2;
+  // holds the node after jump_mid steps: jump_mid_default(), or GCSA2_JUMP_MID=2|6 (any other value is ignored).  Branch
+  // records are written only with jump_mid = 6: where jump_branch_default() says so -- forcing GCSA2_JUMP_MID=6 on a small
+  // image does not switch them on -- or as GCSA2_JUMP_BRANCH=0|1 says.
+  ix->img.jump_tab = nullptr; ix->img.jump_mid = 2; ix->img.jump_branch = 0;
   {
     const char* env = std::getenv("GCSA2_JUMP_TABLE");
     const char* how = std::getenv("GCSA2_JUMP_BUILD");
     const char* mid = std::getenv("GCSA2_JUMP_MID");
+    const char* branch = std::getenv("GCSA2_JUMP_BRANCH");
     size_t free_bytes = 0, total_bytes = 0;
     const u64 n = ix->img.n, bytes = n * sizeof(ulonglong2);
     const bool wanted = (env != nullptr && *env != 0 ? std::atoi(env) != 0 : JUMP_DEFAULT_FIND_ONLY && !ix->img.has_samples);
@@ -1155,8 +1161,11 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       bool doubling = jump_table_fits(2 * bytes, free_bytes, total_bytes);
       if(how != nullptr && std::strcmp(how, "walk") == 0) { doubling = false; }
       if(how != nullptr && std::strcmp(how, "double") == 0) { doubling = true; }        // a failed allocation still ends without a table
-      ix->img.jump_mid = jump_mid_default(n, ix->img.flp != nullptr);
-      if(mid != nullptr && (std::strcmp(mid, "2") == 0 || std::strcmp(mid, "6") == 0)) { ix->img.jump_mid = u32(mid[0] - '0'); }
+      ix->img.jump_mid = u16(jump_mid_default(n, ix->img.flp != nullptr));
+      if(mid != nullptr && (std::strcmp(mid, "2") == 0 || std::strcmp(mid, "6") == 0)) { ix->img.jump_mid = u16(mid[0] - '0'); }
+      bool records = jump_branch_default(n, ix->img.flp != nullptr);
+      if(branch != nullptr && (std::strcmp(branch, "0") == 0 || std::strcmp(branch, "1") == 0)) { records = (branch[0] == '1'); }
+      ix->img.jump_branch = (records && ix->img.jump_mid == 6 ? 1 : 0);
       void* other = nullptr;
       hipError_t e = hipMalloc(&ix->d_jump, bytes);
       if(e == hipSuccess && doubling) { e = hipMalloc(&other, bytes); }
@@ -1174,7 +1183,7 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
         for(u64 first = 0; first < n && e == hipSuccess; first += slice)
         {
           u64 count = (n - first < slice ? n - first : slice);
-          hipLaunchKernelGGL(k_jump_double, dim3(grid_for(count)), dim3(TPB), 0, nullptr, a, n, first, have, ix->img.jump_mid, b);
+          hipLaunchKernelGGL(k_jump_double, dim3(grid_for(count)), dim3(TPB), 0, nullptr, a, n, first, have, u32(ix->img.jump_mid), b);
           e = hipGetLastError();
         }
         std::swap(a, b);
@@ -1190,7 +1199,7 @@ int gcsa2_index_create(const gcsa2_host_view* v, int device, gcsa2_index** out)
       else
       {
         if(ix->d_jump) { (void)hipFree(ix->d_jump); } if(other) { (void)hipFree(other); }
-        ix->d_jump = nullptr; ix->img.jump_mid = 2; (void)hipGetLastError();
+        ix->d_jump = nullptr; ix->img.jump_mid = 2; ix->img.jump_branch = 0; (void)hipGetLastError();
       }
     }
   }
@@ -1461,6 +1470,8 @@ uint64_t gcsa2_kmer_table_k(const gcsa2_index* ix) { return ix->img.kmer_k; }
 uint64_t gcsa2_jump_table_bytes(const gcsa2_index* ix) { return ix->img.jump_tab != nullptr ? ix->img.n * sizeof(ulonglong2) : 0; }
 int gcsa2_jump_mid(const gcsa2_index* ix) { return int(ix->img.jump_mid); }
 int gcsa2_jump_mid_default(uint64_t nodes, int pair_blocks) { return int(jump_mid_default(nodes, pair_blocks != 0)); }
+int gcsa2_jump_branch(const gcsa2_index* ix) { return int(ix->img.jump_branch); }
+int gcsa2_jump_branch_default(uint64_t nodes, int pair_blocks) { return jump_branch_default(nodes, pair_blocks != 0) ? 1 : 0; }
 uint64_t gcsa2_locate_table_bytes(const gcsa2_index* ix) { return ix->img.locate_tab != nullptr ? ix->img.n * sizeof(u64) : 0; }
 
 int gcsa2_lf_device(const gcsa2_index* ix, const uint64_t* d_in, const uint8_t* d_comps, uint64_t nq,

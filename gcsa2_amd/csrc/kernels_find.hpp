@@ -348,7 +348,17 @@ __device__ __forceinline__ PairEnd eval_staged(const ulonglong2* wave_stage, u32
 // slot is zero when len < mid.  Nodes are 36-bit (n < 2^36).
 //   x: [0,36) node after len steps   [36,64) low 28 bits of the node after 4 steps
 //   y: [0,8) its high 8 bits   [8,44) node after mid steps   [44,60) labels (comp - 1), 2 bits per step   [60,64) len
-constexpr u32 JUMP_MAX = 8;
+//
+// Branch record (DevImage::jump_branch, only with mid = 6): a variant of the entry of a chain of len <= 3 steps -- both node
+// slots and every label bit from 2 len on are zero in such an entry -- that ends in front of a node w < n with exactly two
+// incoming labels a < b, both fast characters.  end, labels [0, len) and len keep their meaning (len = 0: v itself is that
+// node and end = v; without records it has the all-zero entry), and
+//   the "after 4" slot holds LF(w, a), the "after mid" slot LF(w, b),
+//   label bits [2 len, 2 len + 2) hold a - 1 and [2 len + 2, 2 len + 4) hold b - 1.
+// An entry is a record exactly when len <= 3 and the label field of step len + 1 is non-zero: b - 1 >= 1 in a record, zero in
+// every other entry, whatever the predecessors are (node 0 included).  B_c has one bit per node and label, so LF of the single
+// node w by a label that enters it is the single node behind that edge, as on the forced part.
+constexpr u32 JUMP_MAX = 8, JUMP_BRANCH_MAX = 3;
 constexpr u64 JUMP_NODE_BITS = 36, JUMP_NODE_MASK = (u64(1) << JUMP_NODE_BITS) - 1;
 __device__ __forceinline__ u64 jt_end(ulonglong2 e) { return e.x & JUMP_NODE_MASK; }
 __device__ __forceinline__ u64 jt_after4(ulonglong2 e) { return (e.x >> 36) | ((e.y & 0xFF) << 28); }
@@ -358,6 +368,12 @@ __device__ __forceinline__ u32 jt_len(ulonglong2 e) { return u32(e.y >> 60); }
 __device__ __forceinline__ ulonglong2 jt_make(u64 end, u64 after4, u64 mid, u32 labels, u32 len)
 {
   return make_ulonglong2(end | (after4 << 36), (after4 >> 28) | (mid << 8) | (u64(labels) << 44) | (u64(len) << 60));
+}
+// branch record: w = the node after the len forced steps, (a, b) its two labels and (pred_a, pred_b) the nodes behind them
+__device__ __forceinline__ bool jt_is_record(ulonglong2 e) { return jt_len(e) <= JUMP_BRANCH_MAX && ((jt_labels(e) >> (2 * jt_len(e) + 2)) & 3) != 0; }
+__device__ __forceinline__ ulonglong2 jt_make_record(u64 w, u64 pred_a, u64 pred_b, u32 labels, u32 len, u32 a, u32 b)
+{
+  return jt_make(w, pred_a, pred_b, labels | ((a - 1) << (2 * len)) | ((b - 1) << (2 * len + 2)), len);
 }
 
 // PAIR = true: two characters per step through the FLP128 pair blocks whenever the next two pattern
@@ -413,6 +429,7 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
   [[maybe_unused]] bool no_jump = false;   // JUMP: no entry can apply for the rest of this pattern
   // JUMP: the two prefixes of a longer chain that an entry offers, {4, 2} or {6, 4} steps (jump_mid = 2 or 6)
   [[maybe_unused]] const u32 take_hi = (img.jump_mid == 6 ? 6u : 4u), take_lo = (img.jump_mid == 6 ? 4u : 2u);
+  [[maybe_unused]] const bool branch = (img.jump_branch != 0);   // JUMP: the table holds branch records (jt_is_record)
   [[maybe_unused]] u64 win_code = 0;       // packed pattern window (see below)
   [[maybe_unused]] u32 win_used = ~u32(0), win_bad = 0;      // characters consumed since the window was loaded (~0: no window)
   [[maybe_unused]] u32 force_single = 0;   // PAIR: characters that must be consumed by single steps (replay)
@@ -686,7 +703,19 @@ __global__ __launch_bounds__(TPB2, JUMP ? JUMP_WAVES : (STATS ? 4 : FIND_WAVES))
         usable = (usable < i ? usable : u32(i));
         u32 take = (usable == len ? len : (usable >= take_hi ? take_hi : (usable >= take_lo ? take_lo : 0u)));
         if(STATS) { jumps++; }
-        if(take > 0)
+        // A branch record whose forced part the pattern follows to its end, with a character left that is one of the two
+        // labels into the node behind it, goes on to that predecessor: len + 1 steps.  Every other case -- another character
+        // there, a bad one, none left, a pattern that leaves the forced part -- treats the record as the ordinary entry of
+        // len steps that it also is: the label bits from 2 len on are never looked at, usable being capped at len.
+        const u32 next_a = (diff >> (2 * len)) & 3, next_b = ((u32(win_code >> (2 * r)) ^ (jt_labels(entry) >> 2)) >> (2 * len)) & 3;
+        if(branch && jt_is_record(entry) && usable == len && i > len && ((win_bad >> (r + len)) & 1) == 0 && (next_a == 0 || next_b == 0))
+        {
+          sp = ep = (next_a == 0 ? jt_after4(entry) : jt_mid(entry));
+          i -= len + 1; win_used += len + 1; done = (i == 0);
+          tried = false;                                       // the predecessor has an entry of its own
+          if(STATS) { steps += len + 1; }
+        }
+        else if(take > 0)
         {
           sp = ep = (take == len ? jt_end(entry) : (take == 4 ? jt_after4(entry) : jt_mid(entry)));
           i -= take; win_used += take; done = (i == 0);
@@ -888,10 +917,16 @@ __global__ __launch_bounds__(TPB) void k_jump_init(DevImage img, u64 first, ulon
   stage_tables(img, t);
   u64 v = first + u64(blockIdx.x) * TPB + threadIdx.x;
   if(v >= img.n) { return; }
-  u32 labels = 0, comp = 0;
-  for(u32 c = 0; c < u32(img.sigma); c++) { if(bv_get(bwt_of(img, c), v)) { labels++; comp = c; } }
+  u32 labels = 0, comp = 0, first_comp = 0;
+  for(u32 c = 0; c < u32(img.sigma); c++) { if(bv_get(bwt_of(img, c), v)) { if(labels == 0) { first_comp = c; } labels++; comp = c; } }
   ulonglong2 e = make_ulonglong2(0, 0);
   if(labels == 1 && comp - 1 < 4) { e = jt_make(lf_node(img, t.C, v), 0, 0, comp - 1, 1); }
+  else if(img.jump_branch != 0 && labels == 2 && first_comp - 1 < 4 && comp - 1 < 4)     // the record of len 0: v is the two-label node
+  {
+    const u64 pred_a = bv_rank(img.edges, clampu(t.C[first_comp] + bv_rank(bwt_of(img, first_comp), v), img.e));
+    const u64 pred_b = bv_rank(img.edges, clampu(t.C[comp] + bv_rank(bwt_of(img, comp), v), img.e));
+    e = jt_make_record(v, pred_a, pred_b, 0, 0, first_comp, comp);
+  }
   table[v] = e;
 }
 
@@ -900,6 +935,9 @@ __global__ __launch_bounds__(TPB) void k_jump_init(DevImage img, u64 first, ulon
 // after 2 steps through every pass; mid = 6 turns it into the node after 6 steps in the last pass (4 -> 8), which reads
 // the previous pass's buffer, where every slot still is "after 2": 6 steps are the 4 of this entry and the first 2 of the
 // entry of the node they reach, if that one has them, and an entry that ends up shorter than 6 gets a zero slot.
+// Branch records (level 1 writes those of len 0 when DevImage::jump_branch is set): a record is final and is copied; a full
+// entry whose next entry is a record takes the record over while the whole chain stays within 3 steps, and otherwise
+// appends the record's forced steps alone.
 __global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restrict__ in, u64 n, u64 first, u32 have, u32 mid,
                                                      ulonglong2* __restrict__ out)
 {
@@ -907,29 +945,42 @@ __global__ __launch_bounds__(TPB) void k_jump_double(const ulonglong2* __restric
   if(v >= n) { return; }
   ulonglong2 e = in[v];
   const bool to6 = (mid == 6 && have == 4);
-  if(jt_len(e) == have)
+  const bool record = jt_is_record(e);                        // final: its chain ends at the two-label node
+  if(jt_len(e) == have && !record)
   {
     const u64 here = jt_end(e);
     u64 after2 = (have == 2 ? here : jt_mid(e)), after4 = (have == 4 ? here : jt_after4(e));
     u64 end = here; u32 labels = jt_labels(e), len = have;
     ulonglong2 next = in[here];
-    if(jt_len(next) > 0)
+    const u32 more = jt_len(next);
+    const bool next_record = jt_is_record(next);
+    if(next_record && have + more <= JUMP_BRANCH_MAX)         // the chain still ends within 3 steps: the record moves to v
     {
-      labels |= jt_labels(next) << (2 * have);
-      end = jt_end(next); len = have + jt_len(next);
-      if(have == 1) { after2 = end; }                        // 1 + 1 steps
+      e = jt_make(jt_end(next), jt_after4(next), jt_mid(next), (labels | (jt_labels(next) << (2 * have))) & 0xFFFF, have + more);
     }
-    if(to6) { after2 = (jt_len(next) >= 2 ? jt_mid(next) : 0); }   // 4 + 2 steps
-    e = jt_make(end, after4, after2, labels & 0xFFFF, len);
+    else
+    {
+      if(more > 0)
+      {
+        labels |= (jt_labels(next) & ((1u << (2 * more)) - 1)) << (2 * have);      // the forced steps only, not a record's two labels
+        end = jt_end(next); len = have + more;
+        if(have == 1) { after2 = end; }                        // 1 + 1 steps
+      }
+      // 4 + 2 steps.  A record's slots are not "after 2": the node after 6 steps is the end of the (full, 4-step) entry of the
+      // node after 2
+      if(to6) { after2 = (more >= 2 ? (next_record ? jt_end(in[jt_mid(e)]) : jt_mid(next)) : 0); }
+      e = jt_make(end, after4, after2, labels & 0xFFFF, len);
+    }
   }
-  else if(to6 && jt_len(e) > 0) { e = jt_make(jt_end(e), jt_after4(e), 0, jt_labels(e), jt_len(e)); }   // len < 4
+  else if(to6 && jt_len(e) > 0 && !record) { e = jt_make(jt_end(e), jt_after4(e), 0, jt_labels(e), jt_len(e)); }   // len < 4
   out[v] = e;
 }
 
 // The same table without a second buffer: every node walks its own forced chain (at most JUMP_MAX steps) and writes its
 // final entry.  What the doubling leaves in an entry is a function of the chain alone -- len = the number of consecutive
 // forced nodes from v on, capped at 8; the node after len steps; the node after 4 steps when len >= 4 and after jump_mid
-// steps when len >= jump_mid, zero otherwise; the labels of the len steps; the all-zero entry when v itself is not forced -- so the
+// steps when len >= jump_mid, zero otherwise; the labels of the len steps; the all-zero entry when v itself is not forced; with
+// jump_branch, the record of a chain of <= 3 steps that stops at a node with two fast labels -- so the
 // two builders write identical bits.  Costs up to 8 dependent LF steps per node against the doubling's 1 + 3 passes; it
 // is what an index takes whose table fits the device but not twice.
 __global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulonglong2* __restrict__ table)
@@ -942,12 +993,20 @@ __global__ __launch_bounds__(TPB) void k_jump_walk(DevImage img, u64 first, ulon
   u32 labels = 0, len = 0;
   while(len < JUMP_MAX && cur < img.n)
   {
-    u32 incoming = 0, comp = 0;
-    u64 rank = 0;
+    u32 incoming = 0, comp = 0, first_comp = 0;
+    u64 rank = 0, first_rank = 0;
     for(u32 c = 0; c < u32(img.sigma); c++)
     {
       u64 r;
-      if(bv_get_rank(bwt_of(img, c), cur, r)) { incoming++; comp = c; rank = r; }
+      if(bv_get_rank(bwt_of(img, c), cur, r)) { if(incoming == 0) { first_comp = c; first_rank = r; } incoming++; comp = c; rank = r; }
+    }
+    if(img.jump_branch != 0 && incoming == 2 && len <= JUMP_BRANCH_MAX && first_comp - 1 < 4 && comp - 1 < 4)
+    {
+      // the chain ends in front of a two-label node within 3 steps: a branch record with the node behind either label
+      const u64 pred_a = bv_rank(img.edges, clampu(t.C[first_comp] + first_rank, img.e));
+      const u64 pred_b = bv_rank(img.edges, clampu(t.C[comp] + rank, img.e));
+      table[v] = jt_make_record(cur, pred_a, pred_b, labels, len, first_comp, comp);
+      return;
     }
     if(incoming != 1 || comp - 1 >= 4) { break; }
     cur = bv_rank(img.edges, clampu(t.C[comp] + rank, img.e));         // lf_node() of a node whose only label is comp

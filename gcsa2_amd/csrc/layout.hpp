@@ -74,6 +74,7 @@ namespace g2 {
 
 typedef uint64_t u64;
 typedef uint32_t u32;
+typedef uint16_t u16;
 typedef uint8_t  u8;
 
 constexpr u64 BLOCK_WORDS   = 8;
@@ -118,9 +119,11 @@ struct DevImage
   u32 kmer_k;                  // 0 = no table
   u32 seed_wide;               // ranges of this many path nodes or more are marked instead of stored (2^24 - 1; lower in tests)
   u32 lcp_shift;               // log2(lcp_branching) when that is a power of two (the reference's default 64), else 0
-  u32 jump_mid;                // steps behind the middle node slot of a jump_tab entry: 2 or 6 (in the padding before the pointer)
+  u16 jump_mid;                // steps behind the middle node slot of a jump_tab entry: 2 or 6 (with jump_branch in the padding before the pointer)
+  u16 jump_branch;             // 1: entries of chains of <= 3 steps that end in front of a two-label node are branch records (only with jump_mid = 6)
   const ulonglong2* jump_tab;  // memoised forced LF chains, one 16-byte entry per path node, or nullptr: the nodes after len (0..8),
-                               // 4 and jump_mid steps, the comps (minus 1) of the steps, 2 bits each, and len (kernels_find.hpp)
+                               // 4 and jump_mid steps, the comps (minus 1) of the steps, 2 bits each, and len; a branch record keeps the
+                               // two predecessors of the node after len steps in the two unused slots (kernels_find.hpp)
   const u64* locate_tab;       // memoised locateInternal walk (gcsa.cpp:880-896), one u64 per path node, or nullptr:
                                //   bit 63 set: the walk ends in a node with ONE sample; bits 0-62 = sample + steps
                                //   bit 63 clear: bits 0-39 = firstSample(end node), bits 40-62 = steps

@@ -239,6 +239,15 @@ uint64_t gcsa2_jump_table_bytes(const gcsa2_index* index);
  * `nodes` path nodes with (1) or without (0) pair blocks. */
 int gcsa2_jump_mid(const gcsa2_index* index);
 int gcsa2_jump_mid_default(uint64_t nodes, int pair_blocks);
+/* Branch records: with mid = 6 the entry of a chain of at most 3 steps has two unused node slots.  Where that chain stops in
+ * front of a node with exactly two incoming labels, both fast characters, the slots hold the two predecessors of that node
+ * and a lookup carries a pattern that continues with either label one step past it, without the block fetch of that step.
+ * Ranges are the same either way; the table's size does not change.  Built by default under the rule that gives mid = 6,
+ * and never with mid = 2; GCSA2_JUMP_BRANCH=0|1 (read at create time; any other value is ignored) overrides the rule, so 1
+ * together with GCSA2_JUMP_MID=6 builds them on a small image, which GCSA2_JUMP_MID=6 alone does not.
+ * gcsa2_jump_branch: 1 when this image's table holds records; gcsa2_jump_branch_default: what the rule gives. */
+int gcsa2_jump_branch(const gcsa2_index* index);
+int gcsa2_jump_branch_default(uint64_t nodes, int pair_blocks);
 /* Bytes of the two-characters-per-step blocks (0 = none).  For every ordered pair of fast characters the
  * composition of two LF steps (gcsa.h:155-162 applied twice) is stored as one rank structure of 128-byte
  * blocks over 192 path nodes each (gcsa2_amd/csrc/layout.hpp "FLP128"): find() then consumes two pattern
