@@ -43,6 +43,8 @@ from .binding_chains import (CHAIN_TOP_LIMIT, CHAIN_LOOKBACK_LIMIT, CHAIN_LDS_DE
                              CHAIN_DEFAULTS, CHAIN_EXPORTS, ChainParams, ChainCalls, chain_params, declare_chain_calls)     # include/gcsa2_hip_chains.h
 from .binding_strands import (STRAND_FORWARD, STRAND_REVERSE, STRAND_BOTH, CANONICAL_MINIMIZER, STRAND_EXPORTS, StrandCalls,
                               declare_strand_calls)     # include/gcsa2_hip_strands.h
+from .binding_pairs import (PAIR_TOP_LIMIT, PAIR_FR, PAIR_RF, PAIR_FF, CHAIN_PAIR, PAIR_SUMMARY, PAIR_STATS, PAIR_DEFAULTS, PAIR_EXPORTS, PairParams,
+                            PairCalls, pair_params, declare_pair_calls)     # include/gcsa2_hip_pairs.h
 STATUS = {0: "OK", -1: "INVALID_ARGUMENT", -2: "NO_DEVICE", -3: "OUT_OF_MEMORY", -4: "HIP",
           -5: "MISSING_COMPONENT", -6: "BUFFER_TOO_SMALL"}
 
@@ -226,6 +228,7 @@ def load_library():
     L.gcsa2_minimizer_clusters_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, u64, vp, u64, u64, u64, vp, vp, vp]
     declare_chain_calls(L)
     declare_strand_calls(L)
+    declare_pair_calls(L)
     L.gcsa2_capped_seeds_device.argtypes = [vp, vp, vp, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p, vp]
     L.gcsa2_capped_seeds_batch.argtypes = [vp, u8p, u64p, u64, u64, u64, u64, u64, C.c_int, vp, vp, u64, u64p, vp, vp, u64, u64p]
     L.gcsa2_group_create.argtypes = [C.POINTER(HostView), C.POINTER(i32), i32, C.POINTER(vp)]
@@ -372,7 +375,7 @@ class LoadedHostView:
             pass
 
 
-class GCSA(ChainCalls, StrandCalls):
+class GCSA(ChainCalls, StrandCalls, PairCalls):
     """Device-resident index with the reference's query methods.
 
     Scalar methods (`find`, `LF`, `count`, `locate`, ...) are one-element batches of the batched

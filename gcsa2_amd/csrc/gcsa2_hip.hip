@@ -28,6 +28,7 @@
 //   kernels_classes.hpp k_classes_*           the same ranges, voted per read over classes of node ids (no counterpart)
 //   kernels_clusters.hpp k_clusters_*         per read the top diagonal bands of its seed hits (no counterpart)
 //   kernels_chains.hpp  k_chains_*            per read the top colinear chains of its seed hits (no counterpart)
+//   kernels_pairs.hpp   k_chain_pairs         per read pair the top placements of two mates' chains under a fragment model (no counterpart)
 //                                                                        src/gcsa.cpp:827-842
 //   kernels_kmers.hpp   k_kmer_expand         countKMers                 src/algorithms.cpp:364-421
 //                       k_kmer_compare        compareKMers               src/algorithms.cpp:505-616
@@ -40,6 +41,7 @@
 #include "../../include/gcsa2_hip.h"
 #include "../../include/gcsa2_hip_chains.h"
 #include "../../include/gcsa2_hip_strands.h"
+#include "../../include/gcsa2_hip_pairs.h"
 
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -78,6 +80,7 @@ using namespace g2;
 #include "kernels_classes.hpp"
 #include "kernels_clusters.hpp"
 #include "kernels_chains.hpp"
+#include "kernels_pairs.hpp"
 #include "kernels_kmers.hpp"
 #include "kernels_mailbox.hpp"
 #include "kernels_build.hpp"
@@ -5642,28 +5645,23 @@ int stranded_hits_checks(const gcsa2_index* ix, u64 k, u64 w, int strands, int o
   return locate_checks(ix, 0);
 }
 
-// gcsa2_stranded_minimizer_hits_device after its argument checks (0 < n_patterns < 2^31): the canonical selection into scratch,
-// the searched windows of the strands asked for as keys in group order (k_strand_windows), then what gcsa2_kmer_hits_device
-// does behind its window plan with the 2 n_patterns groups as the reads and k_strand_seeds as the search.
-int stranded_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
-                       int strands, u64 hit_max, int over, gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity,
-                       u64* total_seeds, u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+// The searched windows of a stranded call (0 < n_patterns < 2^31): the canonical selection into scratch, then the windows of the
+// strands asked for as keys in group order (k_strand_windows) -- `goff` (2 n_patterns + 1) and `wins` (`searched` of them) are
+// what kmer_hits_found takes as the window offsets of its "reads" and as its windows.
+int stranded_windows(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
+                     int strands, const char* name, hipStream_t st, u64*& goff, ulonglong2*& wins, u64& searched)
 {
-  Scratch scratch(ix, st);
   u64 *moff = nullptr, total = 0;
   gcsa2_canonical_minimizer* mins = nullptr;
-  const int rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, "stranded_minimizer_hits", st,
-                                  moff, mins, total);
+  const int rc = minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, name, st, moff, mins, total);
   if(rc != GCSA2_OK) { return rc; }
-  const u64 searched = (strands == GCSA2_STRAND_BOTH ? 2 : 1) * total;
+  searched = (strands == GCSA2_STRAND_BOTH ? 2 : 1) * total;
   if(searched >= (u64(1) << 32))
   {
     HIP_TRY(hipStreamSynchronize(st));                       // the placing pass
     scratch.settled = true;
-    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "stranded_minimizer_hits: 2^32 or more searched windows in one call; split the batch");
+    return fail(GCSA2_ERR_BUFFER_TOO_SMALL, std::string(name) + ": 2^32 or more searched windows in one call; split the batch");
   }
-  u64* goff = nullptr;
-  ulonglong2* wins = nullptr;
   HIP_TRY(scratch.get(goff, 2 * n_patterns + 1));
   HIP_TRY(scratch.get(wins, searched));
   if(searched > 0)
@@ -5673,6 +5671,20 @@ int stranded_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const u
                        u32(strands), goff, wins);
     LAUNCH_CHECK("k_strand_windows");
   }
+  return GCSA2_OK;
+}
+
+// gcsa2_stranded_minimizer_hits_device after its argument checks (0 < n_patterns < 2^31): the searched windows, then what
+// gcsa2_kmer_hits_device does behind its window plan with the 2 n_patterns groups as the reads and k_strand_seeds as the search.
+int stranded_hits_core(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
+                       int strands, u64 hit_max, int over, gcsa2_kmer_profile* d_profiles, u64* d_seed_offsets, gcsa2_mem* d_seeds, u64 seed_capacity,
+                       u64* total_seeds, u64* d_hit_offsets, u64* d_hits, u64 hit_capacity, u64* total_hits, hipStream_t st)
+{
+  Scratch scratch(ix, st);
+  u64 *goff = nullptr, searched = 0;
+  ulonglong2* wins = nullptr;
+  const int rc = stranded_windows(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, strands, "stranded_minimizer_hits", st, goff, wins, searched);
+  if(rc != GCSA2_OK) { return rc; }
   return kmer_hits_found(ix, scratch, nullptr, nullptr, 2 * n_patterns, k, 1, goff, searched, nullptr, hit_max, over, d_profiles, d_seed_offsets, d_seeds,
                          seed_capacity, total_seeds, d_hit_offsets, d_hits, hit_capacity, total_hits, st, wins);
 }
@@ -6852,6 +6864,162 @@ int gcsa2_minimizer_chains_batch(const gcsa2_index* ix, const uint8_t* patterns,
 {
   return chains_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, shift, coord_of_bin, n_bins, params, top, members,
                       summaries, stats, "gcsa2_minimizer_chains_batch");
+}
+
+}  // extern "C"
+
+// ==== chain pairs: per read pair the top placements of two mates' chains under a fragment model (kernels_pairs.hpp) ====
+namespace {
+
+// what a pairs call writes
+struct PairsJob { const gcsa2_pair_params* params; gcsa2_chain_pair* top; gcsa2_pair_summary* summaries; };
+
+// what every form refuses of the pair parameters before any device is touched
+int pairs_checks(const gcsa2_index* ix, const gcsa2_pair_params* p, u64 chain_top_n, u64 n_pairs)
+{
+  CHECK_INDEX(ix);
+  if(p == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: params is NULL"); }
+  if(p->orientation > GCSA2_PAIR_FF) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: orientation must be GCSA2_PAIR_FR, GCSA2_PAIR_RF or GCSA2_PAIR_FF"); }
+  if(p->top_n == 0 || p->top_n > GCSA2_PAIR_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: top_n must be 1 .. GCSA2_PAIR_TOP_LIMIT (64)"); }
+  if(chain_top_n == 0 || chain_top_n > GCSA2_PAIR_TOP_LIMIT) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: chain_top_n must be 1 .. GCSA2_PAIR_TOP_LIMIT (64)"); }
+  if(p->min_fragment > p->max_fragment) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: min_fragment exceeds max_fragment"); }
+  if(p->max_fragment >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: max_fragment must be below 2^32"); }
+  if(p->mean_fragment >= (u64(1) << 32)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: mean_fragment must be below 2^32"); }
+  if(p->unit == 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: unit must be at least 1"); }
+  if(p->cost > 65536) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: cost must be at most 65536"); }
+  if(p->min_score >= (u64(1) << 62)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: min_score must be below 2^62"); }
+  if(n_pairs >= (u64(1) << 30)) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: 2^30 or more pairs in one call; split the batch"); }
+  return GCSA2_OK;
+}
+
+// The pair core.  0 < n_pairs < 2^30; `chains` holds 4 n_pairs rows of chain_top_n.  Writes every row and summary and fills every
+// field of *out but `pairs`.  One kernel; the only host round trip is the counters' at the end.  Scratch: 56 bytes.
+int pairs_core(const gcsa2_index* ix, const gcsa2_chain* chains, u64 n_pairs, u64 chain_top_n, const PairsJob& job, gcsa2_pair_stats* out, Scratch& scratch,
+               hipStream_t st)
+{
+  const gcsa2_pair_params& p = *job.params;
+  const PairParams P{p.min_fragment, p.max_fragment, p.mean_fragment, p.unit, p.cost, p.min_score, u32(p.top_n), u32(chain_top_n)};
+  unsigned long long* stat = nullptr;
+  HIP_TRY(scratch.get(stat, PAIR_WORDS));
+  HIP_TRY(hipMemsetAsync(stat, 0, PAIR_WORDS * sizeof(unsigned long long), st));
+  scratch.settled = false;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(chains) | reinterpret_cast<uintptr_t>(job.top)) & 15) == 0;
+  const dim3 grid(unsigned(std::min<u64>((n_pairs + 3) / 4, u64(ix->compute_units) * 8)));
+  const u64* rows = reinterpret_cast<const u64*>(chains);
+  u64 *top = reinterpret_cast<u64*>(job.top), *summaries = reinterpret_cast<u64*>(job.summaries);
+  if(p.orientation == GCSA2_PAIR_FR) { hipLaunchKernelGGL(k_chain_pairs<GCSA2_PAIR_FR>, grid, dim3(TPB), 0, st, rows, n_pairs, P, aligned, top, summaries, stat); }
+  else if(p.orientation == GCSA2_PAIR_RF) { hipLaunchKernelGGL(k_chain_pairs<GCSA2_PAIR_RF>, grid, dim3(TPB), 0, st, rows, n_pairs, P, aligned, top, summaries, stat); }
+  else { hipLaunchKernelGGL(k_chain_pairs<GCSA2_PAIR_FF>, grid, dim3(TPB), 0, st, rows, n_pairs, P, aligned, top, summaries, stat); }
+  LAUNCH_CHECK("k_chain_pairs");
+  unsigned long long host_stat[PAIR_WORDS];
+  HIP_TRY(hipMemcpyAsync(host_stat, stat, sizeof(host_stat), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  scratch.settled = true;
+  out->candidates = host_stat[PAIR_CANDIDATES]; out->proper = host_stat[PAIR_PROPER]; out->kept = host_stat[PAIR_KEPT]; out->ignored = host_stat[PAIR_IGNORED];
+  out->paired = host_stat[PAIR_PAIRED]; out->unique = host_stat[PAIR_UNIQUE]; out->unique_fragment_sum = host_stat[PAIR_FRAGMENT_SUM];
+  return GCSA2_OK;
+}
+
+// what both fused forms refuse before any device is touched: the refusals of the chain calls, of the pair call and of the
+// stranded hits call -- the components it needs last -- and an odd number of reads
+int fused_pairs_checks(const gcsa2_index* ix, u64 n_patterns, u64 k, u64 w, int over, u64 shift, const void* coord_of_bin, u64 n_bins,
+                       const gcsa2_chain_params* chain_params, const gcsa2_pair_params* pair_params, const char* map_name)
+{
+  CHECK_INDEX(ix);
+  const u64 n_groups = (n_patterns < (u64(1) << 32) ? 2 * n_patterns : 0);          // (beyond: the refusal of the reads below)
+  int rc = chains_job_checks(ix, shift, coord_of_bin, n_bins, chain_params, map_name, n_groups);
+  if(rc != GCSA2_OK) { return rc; }
+  rc = pairs_checks(ix, pair_params, chain_params->top_n, 0);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns % 2 != 0) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "minimizer_chain_pairs: n_patterns must be even: the mates of pair p are the reads 2p and 2p + 1"); }
+  const u64 unused = 0;
+  rc = stranded_hits_checks(ix, k, w, GCSA2_STRAND_BOTH, over, &unused, &unused);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns >= (u64(1) << 31)) { return fail(GCSA2_ERR_BUFFER_TOO_SMALL, "minimizer_chain_pairs: 2^31 or more reads in one call; split the batch"); }
+  return GCSA2_OK;
+}
+
+// the statistics of a host form's piece, summed side by side (sum_stats)
+struct PairBatchStats { gcsa2_chain_stats chains; gcsa2_pair_stats pairs; };
+static_assert(sizeof(PairBatchStats) == 15 * sizeof(uint64_t), "sum_stats: a struct of uint64_t counters and nothing else");
+
+}  // namespace
+
+extern "C" {
+
+int gcsa2_chain_pairs_device(const gcsa2_index* ix, const gcsa2_chain* d_chains, uint64_t n_pairs, uint64_t chain_top_n, const gcsa2_pair_params* params,
+                             gcsa2_chain_pair* d_top, gcsa2_pair_summary* d_summaries, gcsa2_pair_stats* stats, void* stream)
+{
+  const int rc = pairs_checks(ix, params, chain_top_n, n_pairs);
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_pairs > 0 && d_chains == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "chain_pairs: d_chains is NULL"); }
+  gcsa2_pair_stats pre{};
+  pre.pairs = n_pairs;
+  return stats_entry("chain_pairs", ix, stats, pre, n_pairs == 0, [&](gcsa2_pair_stats& sums) -> int
+  {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scratch scratch(ix, st);
+    return pairs_core(ix, d_chains, n_pairs, chain_top_n, PairsJob{params, d_top, d_summaries}, &sums, scratch, st);
+  });
+}
+
+int gcsa2_minimizer_chain_pairs_device(const gcsa2_index* ix, const uint8_t* d_patterns, const uint64_t* d_offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                       uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* d_coord_of_bin, uint64_t n_bins,
+                                       const gcsa2_chain_params* chain_params, const gcsa2_pair_params* pair_params, gcsa2_chain* d_chains,
+                                       gcsa2_chain_anchor* d_members, gcsa2_chain_summary* d_chain_summaries, gcsa2_chain_pair* d_top,
+                                       gcsa2_pair_summary* d_summaries, gcsa2_chain_stats* chain_stats, gcsa2_pair_stats* pair_stats, void* stream)
+{
+  const int rc = fused_pairs_checks(ix, n_patterns, k, w, over, shift, d_coord_of_bin, n_bins, chain_params, pair_params, "d_coord_of_bin");
+  if(rc != GCSA2_OK) { return rc; }
+  if(n_patterns > 0 && d_offsets == nullptr) { return fail(GCSA2_ERR_INVALID_ARGUMENT, "minimizer_chain_pairs: d_offsets is NULL"); }
+  PairBatchStats pre{}, both{};
+  pre.chains.groups = 2 * n_patterns; pre.pairs.pairs = n_patterns / 2;
+  const int run = stats_entry("minimizer_chain_pairs", ix, &both, pre, n_patterns == 0, [&](PairBatchStats& sums) -> int
+  {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scratch scratch(ix, st);
+    const u64 n_groups = 2 * n_patterns, top_n = chain_params->top_n;
+    FusedHits f;
+    int step = fused_stranded_hits(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, hit_max, over, "minimizer_chain_pairs", "chains", f, st);
+    if(step != GCSA2_OK) { return step; }
+    gcsa2_chain* rows = d_chains;
+    if(rows == nullptr) { HIP_TRY(scratch.get(rows, n_groups * top_n)); }
+    const ChainsJob job{shift, d_coord_of_bin, n_bins, chain_params, rows, d_members, d_chain_summaries};
+    step = chains_core(ix, f.seed_off, n_groups, f.seeds, f.m, f.hit_off, f.hit_values, f.h, job, &sums.chains, scratch, st);
+    if(step != GCSA2_OK) { return step; }
+    return pairs_core(ix, rows, n_patterns / 2, top_n, PairsJob{pair_params, d_top, d_summaries}, &sums.pairs, scratch, st);
+  });
+  if(run != GCSA2_OK) { return run; }
+  if(chain_stats != nullptr) { *chain_stats = both.chains; }
+  if(pair_stats != nullptr) { *pair_stats = both.pairs; }
+  return GCSA2_OK;
+}
+
+int gcsa2_minimizer_chain_pairs_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, uint64_t n_patterns, uint64_t k, uint64_t w,
+                                      uint64_t hash_seed, uint64_t hit_max, int over, uint64_t shift, const uint64_t* coord_of_bin, uint64_t n_bins,
+                                      const gcsa2_chain_params* chain_params, const gcsa2_pair_params* pair_params, gcsa2_chain* chains,
+                                      gcsa2_chain_anchor* members, gcsa2_chain_summary* chain_summaries, gcsa2_chain_pair* top, gcsa2_pair_summary* summaries,
+                                      gcsa2_chain_stats* chain_stats, gcsa2_pair_stats* pair_stats)
+{
+  const u64 chain_top_n = (chain_params != nullptr ? chain_params->top_n : 0), member_cap = (chain_params != nullptr ? chain_params->member_cap : 0);
+  const u64 top_n = (pair_params != nullptr ? pair_params->top_n : 0);
+  // per pair: four groups of chain rows, member rows and chain summaries, one row of placements and one summary
+  const PieceOutput outs[] = {{chains, 4 * chain_top_n, sizeof(gcsa2_chain)}, {members, 4 * chain_top_n * member_cap, sizeof(gcsa2_chain_anchor)},
+                              {chain_summaries, 4, sizeof(gcsa2_chain_summary)}, {top, top_n, sizeof(gcsa2_chain_pair)}, {summaries, 1, sizeof(gcsa2_pair_summary)}};
+  PairBatchStats sums{};
+  const int rc = anchors_batch(ix, patterns, offsets, n_patterns, AnchorWindows{k, 1, true, w, hash_seed, hit_max, over}, coord_of_bin, n_bins, outs, &sums,
+                               "gcsa2_minimizer_chain_pairs_batch",
+                               [&] { return fused_pairs_checks(ix, n_patterns, k, w, over, shift, coord_of_bin, n_bins, chain_params, pair_params, "coord_of_bin"); },
+                               [&](const ReadPiece& p, const u8* d_pat, const u64* d_off, const u64* d_map, void* const* d, PairBatchStats* done) -> int
+  {
+    return gcsa2_minimizer_chain_pairs_device(ix, d_pat, d_off, p.count, k, w, hash_seed, hit_max, over, shift, d_map, n_bins, chain_params, pair_params,
+                                              static_cast<gcsa2_chain*>(d[0]), static_cast<gcsa2_chain_anchor*>(d[1]), static_cast<gcsa2_chain_summary*>(d[2]),
+                                              static_cast<gcsa2_chain_pair*>(d[3]), static_cast<gcsa2_pair_summary*>(d[4]), &done->chains, &done->pairs, p.stream);
+  }, 2);
+  if(rc != GCSA2_OK) { return rc; }
+  if(chain_stats != nullptr) { *chain_stats = sums.chains; }
+  if(pair_stats != nullptr) { *pair_stats = sums.pairs; }
+  return GCSA2_OK;
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // and write a top row and a summary per group.  Here, once: the plan with its host round trip (anchors_plan), the two launch
 // shapes of the LDS kernels (anchors_lds_launches), the head of the large path (anchors_large_offsets), the tail that brings
 // the counters home (anchors_tail), the argument checks of the seed forms (seed_form_checks), the fused entry points
-// (fused_hits, fused_anchors_entry) and the host forms (anchors_batch).  clusters_core and chains_core (gcsa2_hip.hip) keep
+// (fused_hits, fused_stranded_hits, fused_anchors_entry) and the host forms (anchors_batch).  clusters_core and chains_core (gcsa2_hip.hip) keep
 // what is theirs: the sorts, scans and score of the clusters, the sorts, dynamic program and finish of the chains.
 // Host code only.  Part of the single translation unit gcsa2_hip.hip, which includes it once Scratch, stats_entry, the hits
 // calls (kmer_hits_found, minimizer_select) and the kernels of kernels_clusters.hpp are defined.
@@ -128,32 +128,28 @@ int seed_form_checks(const std::string& name, const void* goff, u64 n_groups, co
 // the first run reported.  `name` is the call's ("kmer_clusters"), `what` heads the refusal of 2^32 seeds or hits.
 struct FusedHits { u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0; gcsa2_mem* seeds = nullptr; };
 
-int fused_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
-               u64 w, u64 hash_seed, u64 hit_max, int over, const char* name, const char* what, FusedHits& out, hipStream_t st)
+// Behind the windows: `total` of them with the offsets `woff` over n_groups "reads" (kmer_hits_found: at j stride, at the
+// positions of `mins`, or the keys of `wins` -- the groups of a stranded call).
+int fused_hits_found(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_groups, u64 k, u64 stride, const u64* woff,
+                     u64 total, const gcsa2_minimizer* mins, const ulonglong2* wins, u64 hit_max, int over, const char* what, FusedHits& out, hipStream_t st)
 {
-  u64 *woff = nullptr, total = 0;
-  gcsa2_minimizer* mins = nullptr;
-  int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, name, st,
-                                          woff, mins, total)
-                       : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, name, st, woff, total));
-  if(rc != GCSA2_OK) { return rc; }
   u64 *seed_off = nullptr, *hit_off = nullptr, *hit_values = nullptr, m = 0, h = 0;
   gcsa2_mem* seeds = nullptr;
   u64 room = std::max<u64>(4 * total, 1024);
   if(hit_max > 0 && hit_max < 4) { room = std::max<u64>(hit_max * total, 1); }
-  HIP_TRY(scratch.get(seed_off, n_patterns + 1));
+  HIP_TRY(scratch.get(seed_off, n_groups + 1));
   HIP_TRY(scratch.get(seeds, total));
   HIP_TRY(scratch.get(hit_off, total + 1));
   HIP_TRY(scratch.get(hit_values, room));
-  rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
-                       total, &m, hit_off, hit_values, room, &h, st);
+  int rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_groups, k, stride, woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
+                           total, &m, hit_off, hit_values, room, &h, st, wins);
   if(rc == GCSA2_ERR_BUFFER_TOO_SMALL && m <= total && h > room)
   {
     room = h;
     HIP_TRY(scratch.get(hit_values, room));
     g_error.clear();
-    rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
-                         total, &m, hit_off, hit_values, room, &h, st);
+    rc = kmer_hits_found(ix, scratch, d_patterns, d_offsets, n_groups, k, stride, woff, total, mins, hit_max, over, nullptr, seed_off, seeds,
+                         total, &m, hit_off, hit_values, room, &h, st, wins);
   }
   if(rc != GCSA2_OK) { return rc; }
   if(m >= (u64(1) << 32) || h >= (u64(1) << 32))
@@ -162,6 +158,30 @@ int fused_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_pattern
   }
   out.seed_off = seed_off; out.seeds = seeds; out.hit_off = hit_off; out.hit_values = hit_values; out.m = m; out.h = h;
   return GCSA2_OK;
+}
+
+int fused_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 stride, bool minimizers,
+               u64 w, u64 hash_seed, u64 hit_max, int over, const char* name, const char* what, FusedHits& out, hipStream_t st)
+{
+  u64 *woff = nullptr, total = 0;
+  gcsa2_minimizer* mins = nullptr;
+  const int rc = (minimizers ? minimizer_select(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, nullptr, true, nullptr, 0, name, st,
+                                                woff, mins, total)
+                             : window_plan(scratch, d_offsets, n_patterns, k, stride, nullptr, name, st, woff, total));
+  if(rc != GCSA2_OK) { return rc; }
+  return fused_hits_found(ix, scratch, d_patterns, d_offsets, n_patterns, k, (minimizers ? 1 : stride), woff, total, mins, nullptr, hit_max, over, what, out, st);
+}
+
+// The same on both strands of every read (gcsa2_stranded_minimizer_hits_device's own core, 0 < n_patterns < 2^31): the seed CSR
+// has 2 n_patterns groups.
+int fused_stranded_hits(const gcsa2_index* ix, Scratch& scratch, const uint8_t* d_patterns, const uint64_t* d_offsets, u64 n_patterns, u64 k, u64 w, u64 hash_seed,
+                        u64 hit_max, int over, const char* name, const char* what, FusedHits& out, hipStream_t st)
+{
+  u64 *goff = nullptr, searched = 0;
+  ulonglong2* wins = nullptr;
+  const int rc = stranded_windows(ix, scratch, d_patterns, d_offsets, n_patterns, k, w, hash_seed, GCSA2_STRAND_BOTH, name, st, goff, wins, searched);
+  if(rc != GCSA2_OK) { return rc; }
+  return fused_hits_found(ix, scratch, nullptr, nullptr, 2 * n_patterns, k, 1, goff, searched, nullptr, wins, hit_max, over, what, out, st);
 }
 
 // the windows of a fused or host form: every stride-th k-mer, or the (w, k)-minimizers
@@ -201,16 +221,19 @@ int fused_anchors_entry(const gcsa2_index* ix, const uint8_t* d_patterns, const 
   });
 }
 
-// one output array of a host form: per_read records of `size` bytes for every read; not asked for without a host pointer or records
+// one output array of a host form: per_read records of `size` bytes for every read (for every unit of reads, where the form has
+// such units: anchors_batch); not asked for without a host pointer or records
 struct PieceOutput { void* host; u64 per_read; size_t size; };
 
 // The host forms (`name`: the whole "gcsa2_kmer_clusters_batch").  The coordinate map goes to the device once; each piece
 // (for_read_pieces) is one fused device call on its thread's stream -- call(piece, d_patterns, d_offsets, d_map, d_outs,
 // stats) -> status, d_outs[i] the device array of outs[i] or nullptr -- into device arrays of its own, copied to the piece's
-// place in the caller's arrays.
+// place in the caller's arrays.  `unit` > 1 (the chain pairs: 2): the reads come in units of that many, n_patterns is a multiple
+// of it (checks() refuses anything else), a piece holds whole units -- the cut is read_cut over every unit-th offset -- and an
+// output has its per_read records per unit.  Stats may be several structs of counters side by side.
 template<class Stats, size_t N, class Checks, class Call>
 int anchors_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t* offsets, u64 n_patterns, const AnchorWindows& win, const uint64_t* coord_of_bin,
-                  u64 n_bins, const PieceOutput (&outs)[N], Stats* stats, const char* name, Checks checks, Call call)
+                  u64 n_bins, const PieceOutput (&outs)[N], Stats* stats, const char* name, Checks checks, Call call, u64 unit = 1)
 {
   int rc = checks();
   if(rc != GCSA2_OK) { return rc; }
@@ -232,7 +255,15 @@ int anchors_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t
   DBuf<u64> d_map;
   HIP_TRY(d_map.alloc(n_bins));
   HIP_TRY(hipMemcpy(d_map.p, coord_of_bin, n_bins * sizeof(u64), hipMemcpyHostToDevice));
-  const std::vector<u64> cut = read_cut(ix, offsets, n_patterns);
+  std::vector<u64> cut;
+  if(unit == 1) { cut = read_cut(ix, offsets, n_patterns); }
+  else
+  {
+    std::vector<u64> unit_offsets(n_patterns / unit + 1);
+    for(u64 i = 0; i < unit_offsets.size(); i++) { unit_offsets[i] = offsets[i * unit]; }
+    cut = read_cut(ix, unit_offsets.data(), n_patterns / unit);
+    for(u64& at : cut) { at *= unit; }
+  }
   std::vector<Stats> done(cut.size() - 1);
   rc = for_read_pieces(ix, offsets, cut, [&](const ReadPiece& p, Outcome& out) -> bool
   {
@@ -242,7 +273,7 @@ int anchors_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t
     hipError_t e = hipSuccess;
     for(size_t i = 0; i < N; i++)
     {
-      if(e == hipSuccess && outs[i].host != nullptr && outs[i].per_read > 0) { e = d_out[i].alloc(p.count * outs[i].per_read * outs[i].size); }
+      if(e == hipSuccess && outs[i].host != nullptr && outs[i].per_read > 0) { e = d_out[i].alloc(p.count / unit * outs[i].per_read * outs[i].size); }
       d_outs[i] = d_out[i].p;
     }
     if(e != hipSuccess) { out.hip_error("upload of a piece", e); return false; }
@@ -251,7 +282,7 @@ int anchors_batch(const gcsa2_index* ix, const uint8_t* patterns, const uint64_t
     for(size_t i = 0; i < N; i++)
     {
       const size_t read_bytes = outs[i].per_read * outs[i].size;
-      if(e == hipSuccess && d_outs[i] != nullptr) { e = hipMemcpy(static_cast<u8*>(outs[i].host) + p.b * read_bytes, d_outs[i], p.count * read_bytes, hipMemcpyDeviceToHost); }
+      if(e == hipSuccess && d_outs[i] != nullptr) { e = hipMemcpy(static_cast<u8*>(outs[i].host) + p.b / unit * read_bytes, d_outs[i], p.count / unit * read_bytes, hipMemcpyDeviceToHost); }
     }
     if(e != hipSuccess) { out.hip_error("download of a piece", e); return false; }
     return true;

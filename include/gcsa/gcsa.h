@@ -15,6 +15,7 @@
 #include "support.h"
 #include "../gcsa2_hip_chains.h"
 #include "../gcsa2_hip_strands.h"
+#include "../gcsa2_hip_pairs.h"
 
 namespace gcsa
 {
@@ -24,6 +25,13 @@ struct ChainParameters
 {
   size_type band = 64, max_gap = 5000, lookback = 16, match = 1, gap = 1, min_score = 0, top_n = 5, member_cap = 0;
   gcsa2_chain_params c() const { return gcsa2_chain_params{band, max_gap, lookback, match, gap, min_score, top_n, member_cap}; }
+};
+
+// The parameters of the chain-pair calls (gcsa2_pair_params), with the defaults of the Python binding.
+struct PairParameters
+{
+  size_type orientation = GCSA2_PAIR_FR, min_fragment = 0, max_fragment = 1000, mean_fragment = 400, unit = 16, cost = 1, min_score = 0, top_n = 2;
+  gcsa2_pair_params c() const { return gcsa2_pair_params{orientation, min_fragment, max_fragment, mean_fragment, unit, cost, min_score, top_n}; }
 };
 
 class GCSA
@@ -663,6 +671,48 @@ public:
     const int rc = gcsa2_seed_chains_device(handle, d_group_offsets, n_groups, d_seeds, n_seeds, d_hit_offsets, d_hits, n_hits, shift, d_coord_of_bin,
                                             n_bins, &params, d_top, d_members, d_summaries, stats, stream);
     check(rc, "GCSA::seed_chains_device()");
+  }
+
+  // Chain pairs (gcsa2_minimizer_chain_pairs_batch): the reads are interleaved mates, pair p the reads 2p and 2p + 1 (an odd
+  // number of reads is refused).  Both strands of every read are seeded at its canonical (w, k)-minimizers and chained -- chains
+  // (2 reads x chain top_n; group 2q + s is strand s of read q), members and chain_summaries (one per group) as for
+  // minimizer_chains_batch --, and per pair the top_n (1 .. GCSA2_PAIR_TOP_LIMIT) placements of a chain of one mate and a chain of
+  // the other under the fragment model of pair_parameters -- larger score first, then the smaller deviation from the mean
+  // fragment; all zero behind the last placement -- go to top (pairs x top_n), {candidates, proper, kept, ignored, the best chain
+  // of each mate} to summaries (one per pair).  All five are resized and WRITTEN.  Needs no LCP array.
+  void minimizer_chain_pairs_batch(const std::vector<std::uint8_t>& patterns, const std::vector<size_type>& offsets, size_type k, size_type w,
+                                   size_type hash_seed, size_type hit_max, bool sample, size_type shift, const std::vector<size_type>& coord_of_bin,
+                                   const ChainParameters& chain_parameters, const PairParameters& pair_parameters, std::vector<gcsa2_chain>& chains,
+                                   std::vector<gcsa2_chain_anchor>& members, std::vector<gcsa2_chain_summary>& chain_summaries,
+                                   std::vector<gcsa2_chain_pair>& top, std::vector<gcsa2_pair_summary>& summaries,
+                                   gcsa2_chain_stats* chain_stats = nullptr, gcsa2_pair_stats* pair_stats = nullptr) const
+  {
+    const size_type np = offsets.empty() ? 0 : offsets.size() - 1;
+    std::uint8_t dummy = 0;
+    size_type dummy_offset = 0;
+    const gcsa2_chain_params params = chain_parameters.c();
+    const gcsa2_pair_params pair_params = pair_parameters.c();
+    this->chain_outputs(2 * np, params, chains, members, chain_summaries);
+    top.assign((np / 2) * (pair_params.top_n <= GCSA2_PAIR_TOP_LIMIT ? pair_params.top_n : 0), gcsa2_chain_pair{0, 0, 0, 0, 0, 0, 0, 0});
+    summaries.assign(np / 2, gcsa2_pair_summary{0, 0, 0, 0, 0, 0, 0, 0});
+    const int rc = gcsa2_minimizer_chain_pairs_batch(handle, patterns.empty() ? &dummy : patterns.data(), offsets.empty() ? &dummy_offset : offsets.data(), np,
+                                                     k, w, hash_seed, hit_max, sample ? GCSA2_MEM_OVER_SAMPLE : GCSA2_MEM_OVER_SKIP, shift,
+                                                     coord_of_bin.empty() ? nullptr : coord_of_bin.data(), coord_of_bin.size(), &params, &pair_params,
+                                                     chains.empty() ? nullptr : chains.data(), members.empty() ? nullptr : members.data(),
+                                                     chain_summaries.empty() ? nullptr : chain_summaries.data(), top.empty() ? nullptr : top.data(),
+                                                     summaries.empty() ? nullptr : summaries.data(), chain_stats, pair_stats);
+    check(rc, "GCSA::minimizer_chain_pairs_batch()");
+  }
+
+  // The placements of chain rows that are already in device memory (gcsa2_chain_pairs_device): d_chains holds the four rows of
+  // every pair, 4 n_pairs x chain_top_n, in the group order of the stranded hits of interleaved mates; raw device pointers;
+  // d_top and d_summaries may be null.
+  void chain_pairs_device(const gcsa2_chain* d_chains, size_type n_pairs, size_type chain_top_n, const PairParameters& parameters, gcsa2_chain_pair* d_top,
+                          gcsa2_pair_summary* d_summaries, gcsa2_pair_stats* stats = nullptr, void* stream = nullptr) const
+  {
+    const gcsa2_pair_params params = parameters.c();
+    const int rc = gcsa2_chain_pairs_device(handle, d_chains, n_pairs, chain_top_n, &params, d_top, d_summaries, stats, stream);
+    check(rc, "GCSA::chain_pairs_device()");
   }
 
   // Sub-MEM reseeding (gcsa2_sub_mem_hits_batch): inside every MEM of mem_hits_batch (mem_offsets, mems) of at least

@@ -10,6 +10,7 @@
 
 #include "../gcsa2_hip_chains.h"
 #include "../gcsa2_hip_strands.h"
+#include "../gcsa2_hip_pairs.h"
 #include "../gcsa/utils.h"
 #include "../gcsa/files.h"
 #include "../gcsa/support.h"
